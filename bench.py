@@ -8,7 +8,13 @@ by the decoder) through the C ABI (pcg_decode_f32) on the GPU.  Frames are
 independent, so ranks shard with no data-path collective; the barrier and the
 max-over-ranks timing go through gloo on the host.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--mode MODE]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--mode MODE] [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the line.  --full adds the
+  legs that take runs of their own: the rocprofv3 traffic passes, the device copy
+  bandwidth, the host-buffer (PCIe-inclusive) rates and the CPU baseline.
+  --dump-outputs DIR writes what the last timed step's decode returned (info bytes, ok
+  flags, SCL path metrics) as DIR/<name>.npy; the frames are seeded, so two builds run
+  with the same arguments decode the same inputs.
   --gpus N > 1 without a torch.distributed.run environment: this process starts N
   rank processes itself (it never touches the GPU), relays rank 0's JSON line and
   fails if any rank fails.
@@ -17,7 +23,7 @@ Prints ONE JSON line on rank 0.
 roofline: `achieved`/`frac` use the algorithmic bytes (LLRs in, info bytes + ok flag
 [+ metrics] out) over the decode time measured with HIP events on the launch
 stream; `traffic` is the FETCH_SIZE/WRITE_SIZE bytes per launch of the same kernel,
-measured by rocprofv3 child runs of this script (--traffic, default at N=1) or read
+measured by rocprofv3 child runs of this script (--full; --traffic, default at N=1) or read
 from profiles/traffic_<mode>.json only when that file names the same kernel and the
 same source digest.
 """
@@ -72,6 +78,12 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--mode", default="scl8", choices=sorted(MODES))
     ap.add_argument("--ebn0", type=float, default=2.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: rocprofv3 traffic passes, device copy "
+                         "bandwidth, host-buffer rates, CPU baseline (each has its own --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (info, ok[, metrics]) as "
+                         "DIR/<name>.npy (float32; a seeded sample of rows beyond 64 MB, listed in rows.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the CPU baseline (0: the job's CPU share, OMP_NUM_THREADS, else every "
@@ -97,6 +109,13 @@ def parse(argv=None):
     a = ap.parse_args(argv)
     if a.single_stream:
         a.in_flight = False
+    if a.traffic and not a.full:
+        ap.error("--traffic is a leg of --full")
+    if a.dump_outputs and a.dry_run:
+        ap.error("--dump-outputs needs a decode (not --dry-run)")
+    if not a.full:  # a plain run: the headline figure only
+        a.traffic = False
+        a.no_cpu_baseline = a.no_host_rate = a.no_copy_bw = True
     return a
 
 
@@ -334,6 +353,34 @@ def cpu_baseline(mode, N, L, frozen, llr, threads):
                 "sample": f"{F} frames of the same workload, 1 thread (oracle restatement)"}
 
 
+# --------------------------------------------------------------------------- outputs
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs: at most this much in all
+DUMP_SEED = 20240611
+
+
+def dump_outputs(torch, np, dirname, rank, arrays):
+    """--dump-outputs: the arrays a decode call returned ({name: device tensor, one row per
+    frame}) as <dirname>/<name>.npy in float32 (rank r > 0: <name>_rank<r>.npy).  Beyond
+    DUMP_BYTES in all, the same seeded sample of rows of every array, their indices in rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    F = next(iter(arrays.values())).shape[0]
+    row_bytes = 8 + sum(4 * (t.numel() // max(F, 1)) for t in arrays.values())
+    rows = None
+    if F * row_bytes > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(F, DUMP_BYTES // row_bytes, replace=False))
+        idx = torch.from_numpy(rows).to(next(iter(arrays.values())).device)
+    sfx = f"_rank{rank}" if rank else ""
+    shapes = {}
+    for name, t in arrays.items():
+        a = (t if rows is None else t.index_select(0, idx)).cpu().numpy().astype(np.float32)
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), a)
+        shapes[name] = list(a.shape)
+    if rows is not None:
+        np.save(os.path.join(dirname, f"rows{sfx}.npy"), rows.astype(np.float64))
+    return {"dir": dirname, "arrays": shapes,
+            "rows": "all" if rows is None else f"seeded sample of {len(rows)} of {F}"}
+
+
 # --------------------------------------------------------------------------- frames
 def device_frames(torch, N, frozen, F, ebn0, seed, crc, dev):
     """Frames generated on the device (config 5 sizes: 2^17 x 4096 LLRs = 2 GiB per GPU):
@@ -396,6 +443,7 @@ def main(argv=None):
 
     S = 1  # batches in flight (--streams)
     in_flight2 = None
+    dumped = None
     if args.dry_run:
         # plumbing only: a host-only plan (classification, no GPU), a sleep as the step
         plan = Plan(N, L, frozen, systematic=True, crc=crc, device=-1, adaptive=adaptive, fixed=fixed)
@@ -491,6 +539,11 @@ def main(argv=None):
         # correctness spot check of the last step (decoded == transmitted fraction)
         fer = float((d_info != d_ref).any(dim=1).float().mean().item())
         ok_rate = float(d_ok.float().mean().item())
+        if args.dump_outputs:
+            # the last timed step's outputs (its stream's buffers)
+            oi, ok, om = outs[(args.steps - 1 if args.steps else max(args.warmup, S) - 1) % S]
+            dumped = dump_outputs(torch, np, args.dump_outputs, rank,
+                                  {"info": oi, "ok": ok, **({"metrics": om} if om is not None else {})})
         # (one stream) the same steps with a second batch in flight on a second stream and plan:
         # reported beside `value`, never as it -- a launch ends with a tail of waves finishing
         # their last codeword group, which the next batch's waves fill
@@ -572,6 +625,8 @@ def main(argv=None):
         head = git_head()
         if head:
             line["git_head"] = head
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if args.dry_run:
             line["dry_run"] = True
         else:

@@ -58,6 +58,54 @@ def test_src_digest_stable_and_traffic_stamp_rejected(tmp_path):
     assert t is None and why == "no measurement"
 
 
+def test_plain_run_keeps_to_the_headline_and_full_adds_the_legs():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "1"])
+    assert a.steps == 5 and not a.full and a.dump_outputs is None
+    assert a.traffic is False and a.no_cpu_baseline and a.no_host_rate and a.no_copy_bw and not a.in_flight
+    f = bench.parse(["--full"])
+    assert f.full and f.traffic is None and not (f.no_cpu_baseline or f.no_host_rate or f.no_copy_bw)
+    g = bench.parse(["--full", "--no-traffic", "--no-cpu-baseline"])
+    assert g.traffic is False and g.no_cpu_baseline and not g.no_host_rate
+    with pytest.raises(SystemExit):
+        bench.parse(["--traffic"])
+    with pytest.raises(SystemExit):
+        bench.parse(["--dry-run", "--dump-outputs", "x"])
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    torch = pytest.importorskip("torch")
+    sys.path.insert(0, ROOT)
+    import bench
+    F = 1000
+    info = torch.arange(F * 8, dtype=torch.int64).reshape(F, 8).to(torch.uint8)
+    ok = (torch.arange(F) % 3 == 0).to(torch.uint8)
+    met = torch.arange(F * 4, dtype=torch.float32).reshape(F, 4) / 7
+    d = bench.dump_outputs(torch, np, str(tmp_path / "a"), 0, {"info": info, "ok": ok, "metrics": met})
+    assert d["rows"] == "all" and d["arrays"] == {"info": [F, 8], "ok": [F], "metrics": [F, 4]}
+    assert sorted(os.listdir(tmp_path / "a")) == ["info.npy", "metrics.npy", "ok.npy"]
+    got = np.load(tmp_path / "a" / "info.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, info.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "metrics.npy"), met.numpy())
+    # over the budget: the same seeded rows of every array, twice the same, within the budget
+    monkeypatch.setattr(bench, "DUMP_BYTES", 6000)
+    for sub in ("b", "c"):
+        bench.dump_outputs(torch, np, str(tmp_path / sub), 0, {"info": info, "ok": ok, "metrics": met})
+    rows = np.load(tmp_path / "b" / "rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < F and np.all(np.diff(rows) > 0)
+    r = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "b" / "info.npy"), info.numpy()[r])
+    assert np.array_equal(np.load(tmp_path / "b" / "ok.npy"), ok.numpy()[r])
+    assert np.array_equal(np.load(tmp_path / "b" / "metrics.npy"), met.numpy()[r])
+    assert sum(np.load(tmp_path / "b" / f).nbytes for f in os.listdir(tmp_path / "b")) <= 6000
+    for f in os.listdir(tmp_path / "b"):
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+    # another rank's files carry its number
+    bench.dump_outputs(torch, np, str(tmp_path / "a"), 1, {"ok": ok})
+    assert os.path.exists(tmp_path / "a" / "ok_rank1.npy")
+
+
 def test_device_decode_rejects_bad_tensors():
     torch = pytest.importorskip("torch")
     from antpolarcodes_amd._native import Plan

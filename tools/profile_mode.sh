@@ -7,7 +7,7 @@ MODE=${1:-scl8}; TAG=${2:-x}; STEPS=${3:-10}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 400 python bench.py --mode $MODE --steps $STEPS > $OUT/$MODE.json 2> $OUT/$MODE.err || exit 1
+timeout -k 10 400 python bench.py --full --mode $MODE --steps $STEPS > $OUT/$MODE.json 2> $OUT/$MODE.err || exit 1
 # the same steps under the kernel tracer (one stream): its bench line is kept, so the trace's
 # average over the timed launches can be checked against that run's own HIP-event time and
 # against the unprofiled line above (tools/reconcile_profile.py)

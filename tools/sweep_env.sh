@@ -10,7 +10,7 @@ i=0
 for cfg in "$@"; do
   i=$((i+1))
   echo "== $cfg" >> $OUT/sweep_$MODE.txt
-  env $cfg timeout -k 10 300 python bench.py --mode $MODE --steps 10 --no-cpu-baseline --no-host-rate --no-copy-bw \
+  env $cfg timeout -k 10 300 python bench.py --full --mode $MODE --steps 10 --no-cpu-baseline --no-host-rate --no-copy-bw \
       > $OUT/sweep_${MODE}_$i.json 2> $OUT/sweep_${MODE}_$i.err || exit 1
   python3 -c "
 import json,sys
