@@ -84,6 +84,10 @@ def lib():
         L.pcg_decode_f32_host.argtypes = [P, P, C.c_uint64, P, P, P]
         L.pcg_decode_f32_soft.argtypes = [P, P, C.c_uint64, P, P, P, P]
         L.pcg_decode_f32_soft_host.argtypes = [P, P, C.c_uint64, P, P, P]
+        L.pcg_plan_create_scan.argtypes = L.pcg_plan_create.argtypes
+        L.pcg_plan_set_scan_iterations.argtypes = [P, C.c_uint32]
+        L.pcg_decode_scan_f32.argtypes = [P, P, C.c_uint64, P, P, P, P, P]
+        L.pcg_decode_scan_f32_host.argtypes = [P, P, C.c_uint64, P, P, P, P]
         L.pcg_plan_describe.argtypes = [P, C.POINTER(PlanDesc)]
         L.pcg_plan_kernel_name.argtypes = [P]
         L.pcg_plan_kernel_name.restype = C.c_char_p
@@ -288,6 +292,52 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+
+class ScanPlan(Plan):
+    """A SCAN plan (pcg_plan_create_scan): the reference's soft-output Decoding::Scan with
+    `iterations` passes per frame.  Besides info and ok it returns the soft codeword and the
+    extrinsic channel information, F x N float32 each."""
+
+    def __init__(self, N, iterations, frozen, systematic=True, crc=8, device=0):
+        fr, fp = _frozen_array(frozen)
+        h = C.c_void_p()
+        _check(lib().pcg_plan_create_scan(C.byref(h), int(N), int(iterations), fp, int(fr.size),
+                                          int(bool(systematic)), int(crc), int(device)))
+        self._h = h
+        self.N, self.L, self.K = int(N), 1, int(N) - int(fr.size)
+        self.iterations = int(iterations)
+        self.kb = (self.K + 7) // 8
+        self.device = device
+        self.fixed = False
+
+    def set_iterations(self, iterations):
+        """Scan::setIterationLimit for later decodes (pcg_plan_set_scan_iterations)."""
+        _check(lib().pcg_plan_set_scan_iterations(self._h, int(iterations)))
+        self.iterations = int(iterations)
+
+    def decode_host(self, llr, want_ok=True, want_soft=True, want_extrinsic=True):
+        """Host arrays: returns (info, ok, soft, extrinsic) (pcg_decode_scan_f32_host); an
+        output not asked for is None."""
+        llr = np.ascontiguousarray(llr, dtype=np.float32).reshape(-1, self.N)
+        F = llr.shape[0]
+        info = np.zeros((F, self.kb), np.uint8)
+        ok = np.zeros(F, np.uint8) if want_ok else None
+        soft = np.zeros((F, self.N), np.float32) if want_soft else None
+        ext = np.zeros((F, self.N), np.float32) if want_extrinsic else None
+        _check(lib().pcg_decode_scan_f32_host(self._h, llr.ctypes.data, F, info.ctypes.data,
+                                              *(None if a is None else a.ctypes.data for a in (ok, soft, ext))))
+        return info, ok, soft, ext
+
+    def decode_device(self, llr, info, ok=None, soft=None, extrinsic=None, stream=None):
+        """Device-resident decode of torch CUDA tensors (pcg_decode_scan_f32): llr float32 F x N,
+        info uint8 F x ceil(K/8), ok uint8 F, soft and extrinsic float32 F x N (each or None)."""
+        import torch
+        F = self._check_io(llr, info, ok, None, torch.float32)
+        _check_tensor("soft", soft, torch.float32, (F, self.N), self.device)
+        _check_tensor("extrinsic", extrinsic, torch.float32, (F, self.N), self.device)
+        _check(lib().pcg_decode_scan_f32(self._h, _ptr(llr), F, _ptr(info), _ptr(ok), _ptr(soft), _ptr(extrinsic),
+                                         _stream(stream, llr)))
 
 
 class Puncturer:

@@ -5,6 +5,7 @@
 #include "kernels.hpp"
 #include "plan.hpp"
 #include "rtc.hpp"
+#include "scan.hpp"
 
 #include <hip/hip_runtime.h>
 #include <emmintrin.h>
@@ -87,6 +88,11 @@ struct pcg_plan {
     hipModule_t rtc_mod = nullptr;
     hipFunction_t rtc_fn = nullptr;
     hipFunction_t rtc_fn_i8 = nullptr; // 8-bit plans: the kernel for int8 channel LLRs (rtc_fn: float LLRs)
+    // SCAN plans (pcg_plan_create_scan; scan.hpp): host.ops holds ScanOp words, host.L = 1
+    bool scan = false;
+    uint32_t scan_iters = 0;
+    float* d_ext = nullptr;       // pcg_decode_scan_f32_host: extrinsic staging
+    uint64_t ext_frames = 0;
 };
 
 // The host-pointer pipeline of pcg_decode_f32_host / pcg_decode_i8_host: chunks of the
@@ -194,6 +200,7 @@ void free_plan_device(pcg_plan* p)
         (void)hipStreamSynchronize(nullptr);
     }
     (void)hipFree(p->d_soft);
+    (void)hipFree(p->d_ext);
     if (p->last_ev)
         (void)hipEventDestroy(p->last_ev);
     p->last_ev = nullptr;
@@ -225,7 +232,7 @@ constexpr uint64_t RTC_AUTO_FRAMES = 8192;
 // 8-bit lane-serial kernels, and both stages of adaptive plans; never with the op profiler.
 bool rtc_capable(const pcg_plan* p)
 {
-    if (p->dev_opprof)
+    if (p->dev_opprof || p->scan)
         return false;
     if (p->host.fixed) // the 8-bit lane-serial kernels (sccs, scl_char)
         return p->host.L > 1 || p->host.sc_kind == 0;
@@ -540,6 +547,8 @@ int pcg_device_count(void)
     return n;
 }
 
+static int plan_finish(pcg_plan** out, pcg_plan* p, int device);
+
 static int plan_create_impl(pcg_plan** out,
                             uint32_t N,
                             uint32_t L,
@@ -680,6 +689,13 @@ static int plan_create_impl(pcg_plan** out,
                           "PCG_SCLC_SL"})
         if (getenv(v))
             p->dev_overrides |= PCG_DEV_LAYOUT;
+    return plan_finish(out, p, device);
+}
+
+// The device half of plan creation: the schedule, info positions and detector model uploaded to
+// `device`, the plan's ordering event and its wave caps.  Owns p: deleted on failure.
+static int plan_finish(pcg_plan** out, pcg_plan* p, int device)
+{
     if (device < 0) { // host-only plan: classification / validation without a GPU
         p->device = -1;
         *out = p;
@@ -716,7 +732,9 @@ static int plan_create_impl(pcg_plan** out,
         return hip_fail(e, "hipMalloc(plan)");
     }
     // wave caps (hipOccupancy) of the lane-serial kernels, once per plan
-    if (h.fixed && h.L == 1 && h.sc_kind == 0) {
+    if (p->scan) {
+        p->wave_cap = pcg::scan_wave_cap(h.N, h.systematic);
+    } else if (h.fixed && h.L == 1 && h.sc_kind == 0) {
         p->wave_cap = pcg::sccs_wave_cap(p->wave_lds_floats, false);
         p->wave_cap_i8 = pcg::sccs_wave_cap(p->wave_lds_floats, true);
     } else if (h.fixed && h.L > 1) {
@@ -862,7 +880,7 @@ int pcg_plan_describe(const pcg_plan* p, pcg_plan_desc* d)
         return fail(PCG_E_ARG, "null argument");
     d->block_length = p->host.N;
     d->info_length = p->host.K;
-    d->list_size = p->host.L;
+    d->list_size = p->scan ? p->scan_iters : p->host.L;
     d->node_count = p->host.node_count;
     d->op_count = (uint32_t)p->host.ops.size();
     d->lds_bytes = p->wave_lds_floats * 4;
@@ -896,6 +914,8 @@ static int plan_specialize(pcg_plan* p, bool wait)
         if (rc != 0 || !rtc_capable(p))
             return rc;
     }
+    if (p->scan)
+        return fail(PCG_E_UNSUPPORTED, "no plan-specialised kernel for SCAN plans");
     if (!rtc_capable(p))
         return fail(PCG_E_UNSUPPORTED, "no plan-specialised kernel for this plan (not with PCG_OPPROF; the "
                                        "8-bit Fast-SSC decoder on its one-codeword-per-wave kernel has none)");
@@ -924,6 +944,43 @@ static int decode_impl(pcg_plan* p,
                        float* soft = nullptr,
                        const int32_t* pmap = nullptr,
                        uint32_t in_stride = 0);
+
+// Scan::decode (scan.cpp:223-297) over F frames: one launch of scan_kernel
+static int decode_scan(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info, uint8_t* ok, float* soft, float* ext,
+                       void* stream)
+{
+    const auto& h = p->host;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    pcg::ScanArgs a{};
+    a.llr = llr;
+    a.F = F;
+    a.ops = p->d_ops;
+    a.nops = (uint32_t)h.ops.size();
+    a.N = h.N;
+    a.log2N = h.log2N;
+    a.K = h.K;
+    a.kb = (h.K + 7) / 8;
+    a.iters = p->scan_iters;
+    a.info_pos = p->d_info_pos;
+    a.crc_c0 = h.crc_c0;
+    a.crc_bits = (uint32_t)h.crc_kind;
+    a.crc_rows = p->d_crc_m + h.crc_m.size();
+    a.systematic = h.systematic;
+    a.info = info;
+    a.ok = ok;
+    a.soft = soft;
+    a.ext = ext;
+    int rc = order_on(p, s);
+    if (rc != 0)
+        return rc;
+    a.units = (uint32_t)pcg::wave_units(F, 64, p->wave_cap);
+    if ((rc = grow_scratch(p, a.units, sizeof(float), s, pcg::scan_slab_floats(h.N, h.systematic))) != 0)
+        return rc;
+    a.slab = p->d_scratch;
+    if ((rc = pcg::launch_scan(a, s)) != 0)
+        return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return mark_done(p, s);
+}
 
 static int decode_adaptive(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info, uint8_t* ok, float* metrics,
                            void* stream, const int8_t* llr8 = nullptr)
@@ -975,6 +1032,8 @@ int pcg_decode_f32(pcg_plan* p,
     if (F > 0xFFFFFFFFull)
         return fail(PCG_E_ARG, "at most 2^32 - 1 frames per call");
     DeviceGuard g(p->device);
+    if (p->scan) // info and ok only; there are no path metrics
+        return decode_scan(p, llr, F, info, ok, nullptr, nullptr, stream);
     if (p->fast)
         return decode_adaptive(p, llr, F, info, ok, metrics, stream);
     return decode_impl(p, llr, F, info, ok, metrics, stream, nullptr, nullptr);
@@ -1105,6 +1164,8 @@ int pcg_decode_i8(pcg_plan* p,
 {
     if (!p)
         return fail(PCG_E_ARG, "null plan");
+    if (p->scan)
+        return fail(PCG_E_UNSUPPORTED, "SCAN plans decode float LLRs only (no 8-bit SCAN)");
     if (!p->host.fixed)
         return fail(PCG_E_ARG, "int8 LLRs need an 8-bit plan (pcg_plan_create_char)");
     if (F == 0)
@@ -1477,6 +1538,8 @@ int pcg_decode_i8_host(pcg_plan* p, const int8_t* llr, uint64_t F, uint8_t* info
 {
     if (!p)
         return fail(PCG_E_ARG, "null plan");
+    if (p->scan)
+        return fail(PCG_E_UNSUPPORTED, "SCAN plans decode float LLRs only (no 8-bit SCAN)");
     if (!p->host.fixed)
         return fail(PCG_E_ARG, "int8 LLRs need an 8-bit plan (pcg_plan_create_char)");
     if (F == 0)
@@ -1499,6 +1562,8 @@ int pcg_decode_f32_host(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info
         return fail(PCG_E_ARG, "null llr/info buffer");
     if (p->device < 0)
         return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
+    if (p->scan)
+        return pcg_decode_scan_f32_host(p, llr, F, info, ok, nullptr, nullptr);
     DeviceGuard g(p->device);
     return decode_host(p, llr, sizeof(float), F, info, ok, metrics);
 }
@@ -1522,6 +1587,11 @@ int pcg_decode_f32_soft(pcg_plan* p,
                         float* soft,
                         void* stream)
 {
+    if (p && p->scan) {
+        if (F != 0 && !soft)
+            return fail(PCG_E_ARG, "null llr/info/soft buffer");
+        return pcg_decode_scan_f32(p, llr, F, info, ok, soft, nullptr, stream);
+    }
     int rc = soft_supported(p);
     if (rc != 0)
         return rc;
@@ -1539,6 +1609,11 @@ int pcg_decode_f32_soft(pcg_plan* p,
 
 int pcg_decode_f32_soft_host(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info, uint8_t* ok, float* soft)
 {
+    if (p && p->scan) {
+        if (F != 0 && !soft)
+            return fail(PCG_E_ARG, "null llr/info/soft buffer");
+        return pcg_decode_scan_f32_host(p, llr, F, info, ok, soft, nullptr);
+    }
     int rc = soft_supported(p);
     if (rc != 0)
         return rc;
@@ -1608,6 +1683,9 @@ int pcg_decode_punctured_f32(pcg_plan* p,
 {
     if (!p || !punc)
         return fail(PCG_E_ARG, "null plan/puncturer");
+    if (p->scan)
+        return fail(PCG_E_UNSUPPORTED, "SCAN plans do not decode punctured frames (depuncture with "
+                                       "pcg_depuncture_f32, then pcg_decode_scan_f32)");
     if (punc->N != p->host.N)
         return fail(PCG_E_ARG, "puncturer parent length != decoder block length");
     if (F == 0)
@@ -1652,6 +1730,156 @@ int pcg_decode_punctured_f32(pcg_plan* p,
                             metrics ? metrics + f0 * h.L : nullptr, stream);
         if (rc != 0)
             return rc;
+    }
+    return PCG_OK;
+}
+
+int pcg_plan_create_scan(pcg_plan** out,
+                         uint32_t N,
+                         uint32_t iterations,
+                         const uint32_t* frozen,
+                         uint32_t n_frozen,
+                         int systematic,
+                         int crc_kind,
+                         int device)
+{
+    if (!out)
+        return fail(PCG_E_ARG, "plan output pointer is null");
+    *out = nullptr;
+    if (iterations > 255)
+        return fail(PCG_E_ARG, "SCAN: at most 255 iterations");
+    auto* p = new pcg_plan();
+    std::string err;
+    const int rc = pcg::build_scan_plan(p->host, N, frozen, n_frozen, systematic, crc_kind, &err);
+    if (rc != 0) {
+        delete p;
+        return fail(rc, err);
+    }
+    p->scan = true;
+    p->scan_iters = iterations;
+    p->host.sc_kind = 0;
+    p->rtc_mode = 0;
+    p->kernel = "scan_kernel";
+    p->wave_lds_floats = pcg::scan_lds_bytes(N) / 4u;
+    p->scratch_floats = pcg::scan_slab_floats(N, p->host.systematic) / 64u; // per codeword
+    return plan_finish(out, p, device);
+}
+
+int pcg_plan_set_scan_iterations(pcg_plan* p, uint32_t iterations)
+{
+    if (!p)
+        return fail(PCG_E_ARG, "null plan");
+    if (!p->scan)
+        return fail(PCG_E_ARG, "not a SCAN plan (pcg_plan_create_scan)");
+    if (iterations > 255)
+        return fail(PCG_E_ARG, "SCAN: at most 255 iterations");
+    p->scan_iters = iterations;
+    return PCG_OK;
+}
+
+int pcg_decode_scan_f32(pcg_plan* p,
+                        const float* llr,
+                        uint64_t F,
+                        uint8_t* info,
+                        uint8_t* ok,
+                        float* soft,
+                        float* extrinsic,
+                        void* stream)
+{
+    if (!p)
+        return fail(PCG_E_ARG, "null plan");
+    if (!p->scan)
+        return fail(PCG_E_ARG, "not a SCAN plan (pcg_plan_create_scan)");
+    if (F == 0)
+        return PCG_OK;
+    if (!llr || !info)
+        return fail(PCG_E_ARG, "null llr/info buffer");
+    if (p->device < 0)
+        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
+    if (F > 0xFFFFFFFFull)
+        return fail(PCG_E_ARG, "at most 2^32 - 1 frames per call");
+    DeviceGuard g(p->device);
+    return decode_scan(p, llr, F, info, ok, soft, extrinsic, stream);
+}
+
+int pcg_decode_scan_f32_host(pcg_plan* p,
+                             const float* llr,
+                             uint64_t F,
+                             uint8_t* info,
+                             uint8_t* ok,
+                             float* soft,
+                             float* extrinsic)
+{
+    if (!p)
+        return fail(PCG_E_ARG, "null plan");
+    if (!p->scan)
+        return fail(PCG_E_ARG, "not a SCAN plan (pcg_plan_create_scan)");
+    if (F == 0)
+        return PCG_OK;
+    if (!llr || !info)
+        return fail(PCG_E_ARG, "null llr/info buffer");
+    if (p->device < 0)
+        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
+    DeviceGuard g(p->device);
+    const uint64_t N = p->host.N, kb = (p->host.K + 7) / 8;
+    // chunks of pcg_decode_f32_host's size (PCG_HOST_CHUNK overrides it), through staging kept
+    // in the plan; the null-stream copies are ordered after the plan's previous decode
+    uint64_t chunk = (uint64_t)env_int("PCG_HOST_CHUNK", 0);
+    if (chunk == 0)
+        chunk = std::min<uint64_t>(65536, std::max<uint64_t>(4096, (64ull << 20) / (N * sizeof(float))));
+    chunk = std::min<uint64_t>(chunk, F);
+    int rc = order_on(p, nullptr);
+    if (rc != 0)
+        return rc;
+    hipError_t e;
+    if (p->stage_frames < chunk || (soft && p->soft_frames < chunk) || (extrinsic && p->ext_frames < chunk)) {
+        if ((e = hipStreamSynchronize(nullptr)) != hipSuccess)
+            return hip_fail(e, "hipStreamSynchronize");
+    }
+    if (p->stage_frames < chunk) {
+        (void)hipFree(p->d_llr);
+        (void)hipFree(p->d_info);
+        (void)hipFree(p->d_ok);
+        p->d_llr = nullptr;
+        p->d_info = nullptr;
+        p->d_ok = nullptr;
+        p->stage_frames = 0;
+        if ((e = hipMalloc(&p->d_llr, chunk * N * sizeof(float))) != hipSuccess ||
+            (e = hipMalloc(&p->d_info, chunk * std::max<uint64_t>(kb, 1))) != hipSuccess ||
+            (e = hipMalloc(&p->d_ok, chunk)) != hipSuccess)
+            return hip_fail(e, "hipMalloc(scan staging)");
+        p->stage_frames = chunk;
+    }
+    if (soft && p->soft_frames < chunk) {
+        (void)hipFree(p->d_soft);
+        p->d_soft = nullptr;
+        p->soft_frames = 0;
+        if ((e = hipMalloc(&p->d_soft, chunk * N * sizeof(float))) != hipSuccess)
+            return hip_fail(e, "hipMalloc(soft codewords)");
+        p->soft_frames = chunk;
+    }
+    if (extrinsic && p->ext_frames < chunk) {
+        (void)hipFree(p->d_ext);
+        p->d_ext = nullptr;
+        p->ext_frames = 0;
+        if ((e = hipMalloc(&p->d_ext, chunk * N * sizeof(float))) != hipSuccess)
+            return hip_fail(e, "hipMalloc(extrinsic information)");
+        p->ext_frames = chunk;
+    }
+    for (uint64_t f0 = 0; f0 < F; f0 += chunk) {
+        const uint64_t n = std::min(chunk, F - f0);
+        if ((e = hipMemcpy(p->d_llr, llr + f0 * N, n * N * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
+            return hip_fail(e, "hipMemcpy(H2D)");
+        if ((rc = decode_scan(p, p->d_llr, n, p->d_info, ok ? p->d_ok : nullptr, soft ? p->d_soft : nullptr,
+                              extrinsic ? p->d_ext : nullptr, nullptr)) != 0)
+            return rc;
+        if ((e = hipMemcpy(info + f0 * kb, p->d_info, n * kb, hipMemcpyDeviceToHost)) != hipSuccess ||
+            (ok && (e = hipMemcpy(ok + f0, p->d_ok, n, hipMemcpyDeviceToHost)) != hipSuccess) ||
+            (soft && (e = hipMemcpy(soft + f0 * N, p->d_soft, n * N * sizeof(float), hipMemcpyDeviceToHost)) !=
+                         hipSuccess) ||
+            (extrinsic && (e = hipMemcpy(extrinsic + f0 * N, p->d_ext, n * N * sizeof(float),
+                                         hipMemcpyDeviceToHost)) != hipSuccess))
+            return hip_fail(e, "hipMemcpy(D2H)");
     }
     return PCG_OK;
 }

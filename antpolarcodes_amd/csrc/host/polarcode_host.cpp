@@ -3,6 +3,7 @@
 // top of the C ABI (include/pcg.h).  No device code here.
 #include <polarcode/construction/constructor.h>
 #include <polarcode/decoding/decoder.h>
+#include <polarcode/decoding/scan.h>
 #include <polarcode/encoding/butterfly_fip_packed.h>
 #include <polarcode/encoding/encoder.h>
 #include <polarcode/errordetection/errordetector.h>
@@ -887,6 +888,132 @@ bool GpuAdaptiveMixed::decodeBatch(const float* llr, size_t F, uint8_t* info, ui
         all = all && okv[f];
     }
     return all;
+}
+
+// ---- Scan (scan.cpp): the soft-output cancellation decoder on the GPU -------------------------
+Scan::Scan(size_t blockLength, unsigned iterationLimit, const std::vector<unsigned>& frozenBits, int device)
+    : mIterationLimit(iterationLimit), mDevice(device)
+{
+    initialize(blockLength, iterationLimit, frozenBits);
+}
+
+Scan::~Scan() { releasePlan(); }
+
+void Scan::releasePlan()
+{
+    if (mPlan)
+        pcg_plan_destroy(mPlan);
+    mPlan = nullptr;
+}
+
+// scan.cpp:31-63: float input and output containers, the packed output bytes
+void Scan::initialize(size_t blockLength, unsigned iterationLimit, const std::vector<unsigned>& frozenBits)
+{
+    Decoder::initialize(blockLength, frozenBits);
+    mIterationLimit = iterationLimit;
+    releasePlan();
+    pcg_plan* probe = nullptr; // validate now, without a GPU
+    const int rc = pcg_plan_create_scan(&probe, (uint32_t)blockLength, iterationLimit, mFrozenBits.data(),
+                                        (uint32_t)mFrozenBits.size(), 1, 0, -1);
+    if (rc != 0)
+        throw_pcg(rc);
+    pcg_plan_destroy(probe);
+    if (!mExternalContainers) {
+        delete mLlrContainer;
+        delete mBitContainer;
+        delete[] mOutputContainer;
+    }
+    mExternalContainers = false;
+    mLlrContainer = new FloatContainer(mBlockLength, mFrozenBits);
+    mBitContainer = new FloatContainer(mBlockLength, mFrozenBits);
+    mOutputContainer = new unsigned char[(mBlockLength + 7) / 8]();
+    mExtrinsic.assign(mBlockLength, 0.0f);
+}
+
+void Scan::setIterationLimit(unsigned iterationLimit)
+{
+    if (iterationLimit > 255)
+        throw std::logic_error("SCAN: at most 255 iterations");
+    mIterationLimit = iterationLimit;
+    if (mPlan)
+        (void)pcg_plan_set_scan_iterations(mPlan, iterationLimit);
+}
+
+void Scan::setErrorDetection(ErrorDetection::Detector* pDetector)
+{
+    if (ErrorDetection::gpuKind(pDetector) < 0)
+        throw std::logic_error("detector " + pDetector->getType() + " cannot be evaluated on the GPU");
+    mErrorDetector = pDetector;
+}
+
+void Scan::ensurePlan()
+{
+    const int kind = ErrorDetection::gpuKind(mErrorDetector);
+    if (mPlan && kind == mPlanKind && mSystematic == mPlanSys)
+        return;
+    releasePlan();
+    const int rc = pcg_plan_create_scan(&mPlan, (uint32_t)mBlockLength, mIterationLimit, mFrozenBits.data(),
+                                        (uint32_t)mFrozenBits.size(), mSystematic ? 1 : 0, kind, mDevice);
+    if (rc != 0) {
+        mPlan = nullptr;
+        throw_pcg(rc);
+    }
+    mPlanKind = kind;
+    mPlanSys = mSystematic;
+}
+
+bool Scan::decode()
+{
+    ensurePlan();
+    uint8_t ok = 0;
+    const int rc = pcg_decode_scan_f32_host(mPlan, static_cast<FloatContainer*>(mLlrContainer)->data(), 1,
+                                            mOutputContainer, &ok, static_cast<FloatContainer*>(mBitContainer)->data(),
+                                            mExtrinsic.data());
+    if (rc != 0)
+        throw_pcg(rc);
+    return ok != 0;
+}
+
+void Scan::getExtrinsicChannelInformation(float* eLlr)
+{
+    std::memcpy(eLlr, mExtrinsic.data(), mBlockLength * sizeof(float));
+}
+
+bool Scan::decodeBatchSoft(const float* llr, size_t F, uint8_t* info, uint8_t* ok, float* soft, float* extrinsic)
+{
+    ensurePlan();
+    std::vector<uint8_t> okv;
+    uint8_t* okp = ok;
+    if (!okp) {
+        okv.assign(F, 0);
+        okp = okv.data();
+    }
+    const int rc = pcg_decode_scan_f32_host(mPlan, llr, F, info, okp, soft, extrinsic);
+    if (rc != 0)
+        throw_pcg(rc);
+    for (size_t f = 0; f < F; ++f)
+        if (!okp[f])
+            return false;
+    return true;
+}
+
+bool Scan::decodeBatch(const float* llr, size_t F, uint8_t* info, uint8_t* ok, float*)
+{
+    return decodeBatchSoft(llr, F, info, ok, nullptr, nullptr);
+}
+
+void Scan::decodeBatchSoftDevice(const float* llr, size_t F, uint8_t* info, uint8_t* ok, float* soft,
+                                 float* extrinsic, void* hipStream)
+{
+    ensurePlan();
+    const int rc = pcg_decode_scan_f32(mPlan, llr, F, info, ok, soft, extrinsic, hipStream);
+    if (rc != 0)
+        throw_pcg(rc);
+}
+
+void Scan::decodeBatchDevice(const float* llr, size_t F, uint8_t* info, uint8_t* ok, float*, void* hipStream)
+{
+    decodeBatchSoftDevice(llr, F, info, ok, nullptr, nullptr, hipStream);
 }
 
 Decoder* makeDecoder(size_t blockLength, size_t listSize, const std::vector<unsigned>& frozenBits, int impl)

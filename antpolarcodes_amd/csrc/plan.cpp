@@ -2,6 +2,7 @@
 #include "plan.hpp"
 
 #include "crc_host.hpp"
+#include "scan.hpp"
 
 #include <cstdlib>
 #include <random>
@@ -339,9 +340,47 @@ void scl_char_emit(PlanHost& p, const std::vector<uint32_t>& f, uint32_t n, uint
     p.ops.push_back(mkop(OP_COMB, n, off));
 }
 
-} // namespace
+// Scan (scan.cpp:80-210) in decode order.  Node (level, group) with frozen set f over its n = N >>
+// level leaves: F-with-O into the left child, <left>, G-with-the-left's-message into the right
+// child, <right>, both messages combined toward the root.  A child whose leaves are all frozen
+// is not visited: its message is +inf (SCAN_EINF / SCAN_OINF on its parent's ops), and only a
+// non-systematic plan has an op for it (its outputs).  Size-2 nodes are one op.
+uint32_t mkscan(uint32_t code, uint32_t level, uint32_t group, uint32_t flags)
+{
+    return code | (level << 4) | (group << 8) | (flags << 24);
+}
 
-int build_plan(PlanHost& p,
+void scan_emit(PlanHost& p, const std::vector<uint32_t>& f, uint32_t n, uint32_t level, uint32_t group)
+{
+    p.node_count++;
+    if (n == 2) {
+        uint32_t fl = 0;
+        for (uint32_t v : f)
+            fl |= v == 0 ? SCAN_EINF : SCAN_OINF;
+        p.ops.push_back(mkscan(SCAN_LEAF2, level, group, fl));
+        return;
+    }
+    const uint32_t h = n / 2;
+    std::vector<uint32_t> lf, rf;
+    split(f, h, lf, rf);
+    const bool lz = lf.size() == h, rz = rf.size() == h;
+    const uint32_t fl = (lz ? SCAN_EINF : 0u) | (rz ? SCAN_OINF : 0u);
+    if (!lz) {
+        p.ops.push_back(mkscan(SCAN_DOWN_L, level, group, fl));
+        scan_emit(p, lf, h, level + 1, 2 * group);
+    } else if (!p.systematic) {
+        p.ops.push_back(mkscan(SCAN_FROZEN, level + 1, 2 * group, 0));
+    }
+    if (!rz) {
+        p.ops.push_back(mkscan(SCAN_DOWN_R, level, group, fl));
+        scan_emit(p, rf, h, level + 1, 2 * group + 1);
+    } else if (!p.systematic) {
+        p.ops.push_back(mkscan(SCAN_FROZEN, level + 1, 2 * group + 1, 0));
+    }
+    p.ops.push_back(mkscan(SCAN_UP, level, group, fl));
+}
+
+int build_impl(PlanHost& p,
                uint32_t N,
                uint32_t L,
                const uint32_t* frozen,
@@ -349,9 +388,18 @@ int build_plan(PlanHost& p,
                int systematic,
                int crc_kind,
                std::string* err,
-               int fixed)
+               int fixed,
+               int scan)
 {
     p = PlanHost();
+    if (scan && (N < 8 || (N & (N - 1)))) {
+        *err = "SCAN: block length must be a power of two >= 8";
+        return -1;
+    }
+    if (scan && N > SCAN_MAX_N) {
+        *err = "SCAN: block lengths above " + std::to_string(SCAN_MAX_N) + " are not supported";
+        return -4;
+    }
     // Fast-SSC float plans run codes down to N = 2 (the reference's own Repetition /
     // SPC KATs start there, decodingtest.cpp:185-195); the lane-serial list and 8-bit
     // kernels need N >= 8
@@ -394,7 +442,9 @@ int build_plan(PlanHost& p,
         p.sc_kind = (k && std::string(k) == "wave") ? 1 : ((k && std::string(k) == "scs") ? 0 : 2);
     }
     try {
-        if (p.fixed && L == 1)
+        if (scan)
+            scan_emit(p, p.frozen, N, 0, 0);
+        else if (p.fixed && L == 1)
             sc_char_emit(p, p.frozen, N, 0);
         else if (p.fixed)
             scl_char_emit(p, p.frozen, N, 0);
@@ -471,6 +521,32 @@ int build_plan(PlanHost& p,
         }
     }
     return 0;
+}
+
+} // namespace
+
+int build_plan(PlanHost& p,
+               uint32_t N,
+               uint32_t L,
+               const uint32_t* frozen,
+               uint32_t nf,
+               int systematic,
+               int crc_kind,
+               std::string* err,
+               int fixed)
+{
+    return build_impl(p, N, L, frozen, nf, systematic, crc_kind, err, fixed, 0);
+}
+
+int build_scan_plan(PlanHost& p,
+                    uint32_t N,
+                    const uint32_t* frozen,
+                    uint32_t nf,
+                    int systematic,
+                    int crc_kind,
+                    std::string* err)
+{
+    return build_impl(p, N, 1, frozen, nf, systematic, crc_kind, err, 0, 1);
 }
 
 } // namespace pcg

@@ -9,12 +9,15 @@ Detector, Puncturer and frozen_bits with the same names, arguments and errors.
     info = dec.decode_batch(llrs)            # (F, N) float32 -> (F, K/8) uint8 on the MI355X
 
 Decoder types "gpu" and "float" run the MI355X kernels (list size < 2 -> Fast-SSC,
-else CRC-aided SCL).  The native module is mandatory: there is no CPU fallback.
+else CRC-aided SCL).  ScanDecoder(blockLength, iterationLimit, frozenBitPositions) is the
+reference's soft-output SCAN decoder (Decoding::Scan) on the MI355X: real per-bit LLRs from
+getSoftCodeword / getExtrinsicChannelInformation and decode_batch(..., return_soft=True); the
+decoder type string "scan" of PolarDecoder is not routed to it yet.  The native module is mandatory: there is no CPU fallback.
 """
 from ._native import _prefer_torch_hip_runtime
 
 _prefer_torch_hip_runtime()  # share PyTorch's HIP runtime (see _native.py)
 
-from ._pypolar import Detector, PolarDecoder, PolarEncoder, Puncturer, frozen_bits  # noqa: E402
+from ._pypolar import Detector, PolarDecoder, PolarEncoder, Puncturer, ScanDecoder, frozen_bits  # noqa: E402
 
-__all__ = ["PolarDecoder", "PolarEncoder", "Detector", "Puncturer", "frozen_bits"]
+__all__ = ["PolarDecoder", "PolarEncoder", "Detector", "Puncturer", "ScanDecoder", "frozen_bits"]

@@ -1,0 +1,62 @@
+"""Time the SCAN kernel on device-resident frames: python -m antpolarcodes_amd.scan_time
+
+HIP events around ScanPlan.decode_device on AWGN frames already on the GPU (N = 1024, K = 512,
+CRC-8, 2^14 frames by default), 3 warm-ups, the median of 20 runs, at 1 and 4 iterations, with
+info and ok only and again with the soft codeword.  Prints one JSON line per configuration.
+"""
+import argparse
+import json
+import statistics
+
+import numpy as np
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--n", type=int, default=1024)
+    ap.add_argument("--k", type=int, default=512)
+    ap.add_argument("--frames", type=int, default=1 << 14)
+    ap.add_argument("--iterations", type=int, nargs="+", default=[1, 4])
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--runs", type=int, default=20)
+    ap.add_argument("--ebn0", type=float, default=2.0)
+    a = ap.parse_args()
+
+    import torch
+
+    from . import frames
+    from ._native import ScanPlan
+    from .construction import frozen_bits
+
+    fr = frozen_bits(a.n, a.k, 0.0)
+    base = min(a.frames, 1024)  # host-generated frames, tiled on the device
+    llr, _, _ = frames.awgn_frames(a.n, fr, base, a.ebn0, seed=1, crc=8)
+    dev = torch.device("cuda:0")
+    x = torch.from_numpy(np.ascontiguousarray(llr)).to(dev).repeat((a.frames + base - 1) // base, 1)[:a.frames]
+    x = x.contiguous()
+    plan = ScanPlan(a.n, 1, fr, crc=8)
+    info = torch.empty((a.frames, plan.kb), dtype=torch.uint8, device=dev)
+    ok = torch.empty((a.frames,), dtype=torch.uint8, device=dev)
+    soft = torch.empty((a.frames, a.n), dtype=torch.float32, device=dev)
+    d = plan.describe()
+    for it in a.iterations:
+        plan.set_iterations(it)
+        for want_soft in (False, True):
+            ms = []
+            for r in range(a.warmup + a.runs):
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                plan.decode_device(x, info, ok, soft if want_soft else None)
+                t1.record()
+                t1.synchronize()
+                if r >= a.warmup:
+                    ms.append(t0.elapsed_time(t1))
+            med = statistics.median(ms)
+            print(json.dumps({"kernel": plan.kernel_name(), "N": a.n, "K": a.k, "frames": a.frames, "iterations": it,
+                              "soft": want_soft, "ms": round(med, 4), "cw_per_s": round(a.frames / (med * 1e-3), 1),
+                              "ok_rate": round(float(ok.float().mean()), 4), "lds_bytes": d["lds_bytes"],
+                              "scratch_bytes_per_codeword": d["scratch_bytes"]}))
+
+
+if __name__ == "__main__":
+    main()

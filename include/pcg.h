@@ -29,6 +29,12 @@
  *                        batched, device-resident int8 LLRs
  *   pcg_decode_i8_host <- the same with host buffers
  *   pcg_plan_create_adaptive_char <- AdaptiveChar, adaptive_char.cpp:14-45
+ *   pcg_plan_create_scan <- new Decoding::Scan(N, iterationLimit, frozen), Scan::initialize
+ *                        (src/polarcode/decoding/scan.cpp:17-63) + setSystematic / setErrorDetection
+ *   pcg_plan_set_scan_iterations <- Scan::setIterationLimit scan.cpp:26-29
+ *   pcg_decode_scan_f32[_host] <- Scan::decode scan.cpp:223-297 (updatellrmap :80-126,
+ *                        updatebitmap :128-210), Decoder::getSoftCodeword, and
+ *                        Scan::getExtrinsicChannelInformation scan.cpp:299-304, batched
  *   pcg_plan_destroy  <- Decoder::~Decoder decoder.cpp:104-114
  *   pcg_last_error    <- the std::exception text the reference throws
  *   pcg_puncturer_*   <- PolarCode::Puncturer (include/polarcode/puncturer.h:33-99,
@@ -239,6 +245,57 @@ int pcg_decode_i8_host(pcg_plan* plan,
                        uint8_t* info,
                        uint8_t* ok,
                        float* metrics);
+
+/* ---- SCAN: the soft-output cancellation decoder (Decoding::Scan, scan.cpp) ----------------
+ * A SCAN plan runs `iterations` (0 .. 255) passes of the reference's message schedule over each
+ * frame and returns real per-bit LLRs: the soft codeword (channel + extrinsic for systematic
+ * plans, the per-leaf sums for non-systematic ones) and the extrinsic channel information.
+ * Every frame starts from zeroed state: nothing carries between frames or calls.  All outputs
+ * equal the reference's bit for bit, signed zeros and infinities included (a non-systematic
+ * decode with 0 iterations returns +0.0, a freshly constructed reference decoder's output).
+ * Contract: finite LLRs whose sums stay finite -- outside that the reference itself produces
+ * NaN, and the pruning of all-frozen subtrees here need not reproduce it.
+ * N: a power of two, 8 <= N <= 4096 (PCG_E_UNSUPPORTED above); any strictly ascending frozen
+ * set (PCG_E_FROZEN never applies).  pcg_plan_describe reports list_size = iterations (as
+ * Scan::getListSize does), lds_bytes of a wave and scratch_bytes per codeword;
+ * pcg_plan_kernel_name is "scan_kernel".  There is no specialised kernel, no 8-bit form and no
+ * punctured decode: pcg_plan_specialize[_async], pcg_decode_i8[_host] and
+ * pcg_decode_punctured_f32 return PCG_E_UNSUPPORTED.  pcg_decode_f32[_host] on a SCAN plan
+ * writes info and ok (metrics is ignored); pcg_decode_f32_soft[_host] also the soft codeword. */
+int pcg_plan_create_scan(pcg_plan** plan,
+                         uint32_t N,
+                         uint32_t iterations,
+                         const uint32_t* frozen,
+                         uint32_t n_frozen,
+                         int systematic,
+                         int crc_kind,
+                         int device);
+
+/* Scan::setIterationLimit: the iteration count of later decodes (0 .. 255). */
+int pcg_plan_set_scan_iterations(pcg_plan* plan, uint32_t iterations);
+
+/* Decode F frames with a SCAN plan (PCG_E_ARG for any other plan).  Device pointers,
+ * asynchronous, stream-ordered like pcg_decode_f32.  info: F x ceil(K/8) bytes, the sign bits
+ * of the soft codeword at the information positions, MSB-first.  ok (F bytes), soft and
+ * extrinsic (F x N floats each, natural order) may be NULL: an output not asked for costs no
+ * stores. */
+int pcg_decode_scan_f32(pcg_plan* plan,
+                        const float* llr,
+                        uint64_t F,
+                        uint8_t* info,
+                        uint8_t* ok,
+                        float* soft,
+                        float* extrinsic,
+                        void* stream);
+
+/* Same with HOST pointers; synchronous.  Streams the batch through device buffers in chunks. */
+int pcg_decode_scan_f32_host(pcg_plan* plan,
+                             const float* llr,
+                             uint64_t F,
+                             uint8_t* info,
+                             uint8_t* ok,
+                             float* soft,
+                             float* extrinsic);
 
 int pcg_plan_describe(const pcg_plan* plan, pcg_plan_desc* desc);
 

@@ -258,8 +258,9 @@ public:
 };
 
 /// makeDecoder (decoder.cpp:54-87): decoder_impl 1 = float (Fast-SSC for listSize 1, else
-/// SCL), 2 = AdaptiveFloat (listSize >= 2), 3 = SCAN (not part of this build:
-/// std::logic_error), every other value = the 8-bit decoders (FastSscFipChar / SclFipChar),
+/// SCL), 2 = AdaptiveFloat (listSize >= 2), 3 = SCAN (not routed here yet: std::logic_error --
+/// the decoder itself exists, construct Decoding::Scan from <polarcode/decoding/scan.h>; routing
+/// this value and create's "scan" to it is a follow-up), every other value = the 8-bit decoders (FastSscFipChar / SclFipChar),
 /// the default 0 included.  Always installs a CRC-8 detector (the reference's Q5 behaviour).
 Decoder* makeDecoder(size_t blockLength, size_t listSize, const std::vector<unsigned>& frozenBits,
                      int decoder_impl = 0);
