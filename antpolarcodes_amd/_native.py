@@ -88,6 +88,10 @@ def lib():
         L.pcg_plan_set_scan_iterations.argtypes = [P, C.c_uint32]
         L.pcg_decode_scan_f32.argtypes = [P, P, C.c_uint64, P, P, P, P, P]
         L.pcg_decode_scan_f32_host.argtypes = [P, P, C.c_uint64, P, P, P, P]
+        L.pcg_plan_create_fsscan.argtypes = L.pcg_plan_create.argtypes
+        L.pcg_plan_set_fsscan_trials.argtypes = [P, C.c_uint32, C.c_int]
+        L.pcg_decode_fsscan_f32.argtypes = [P, P, C.c_uint64, P, P, P, P, P]
+        L.pcg_decode_fsscan_f32_host.argtypes = [P, P, C.c_uint64, P, P, P, P]
         L.pcg_plan_describe.argtypes = [P, C.POINTER(PlanDesc)]
         L.pcg_plan_kernel_name.argtypes = [P]
         L.pcg_plan_kernel_name.restype = C.c_char_p
@@ -338,6 +342,54 @@ class ScanPlan(Plan):
         _check_tensor("extrinsic", extrinsic, torch.float32, (F, self.N), self.device)
         _check(lib().pcg_decode_scan_f32(self._h, _ptr(llr), F, _ptr(info), _ptr(ok), _ptr(soft), _ptr(extrinsic),
                                          _stream(stream, llr)))
+
+
+class FastSscanPlan(Plan):
+    """A Fast-SSCAN plan (pcg_plan_create_fsscan): the reference's Decoding::FastSscanFloat, SCAN
+    with closed-form subtrees whose passes repeat only while the frame's detector check fails, up
+    to `trials`.  Returns info, ok, the soft codeword (F x N float32) and the passes run per
+    frame (uint8)."""
+
+    def __init__(self, N, trials, frozen, systematic=True, crc=8, device=0):
+        fr, fp = _frozen_array(frozen)
+        h = C.c_void_p()
+        _check(lib().pcg_plan_create_fsscan(C.byref(h), int(N), int(trials), fp, int(fr.size),
+                                            int(bool(systematic)), int(crc), int(device)))
+        self._h = h
+        self.N, self.L, self.K = int(N), 1, int(N) - int(fr.size)
+        self.trials, self.forced = int(trials), False
+        self.kb = (self.K + 7) // 8
+        self.device = device
+        self.fixed = False
+
+    def set_trials(self, trials, forced=False):
+        """The trial limit of later decodes; forced: exactly that many passes, the check only
+        after the last (pcg_plan_set_fsscan_trials)."""
+        _check(lib().pcg_plan_set_fsscan_trials(self._h, int(trials), int(bool(forced))))
+        self.trials, self.forced = int(trials), bool(forced)
+
+    def decode_host(self, llr, want_ok=True, want_soft=True, want_trials=True):
+        """Host arrays: returns (info, ok, soft, trials) (pcg_decode_fsscan_f32_host); an output
+        not asked for is None."""
+        llr = np.ascontiguousarray(llr, dtype=np.float32).reshape(-1, self.N)
+        F = llr.shape[0]
+        info = np.zeros((F, self.kb), np.uint8)
+        ok = np.zeros(F, np.uint8) if want_ok else None
+        soft = np.zeros((F, self.N), np.float32) if want_soft else None
+        trials = np.zeros(F, np.uint8) if want_trials else None
+        _check(lib().pcg_decode_fsscan_f32_host(self._h, llr.ctypes.data, F, info.ctypes.data,
+                                                *(None if a is None else a.ctypes.data for a in (ok, soft, trials))))
+        return info, ok, soft, trials
+
+    def decode_device(self, llr, info, ok=None, soft=None, trials=None, stream=None):
+        """Device-resident decode of torch CUDA tensors (pcg_decode_fsscan_f32): llr float32 F x N,
+        info uint8 F x ceil(K/8), ok and trials uint8 F, soft float32 F x N (each or None)."""
+        import torch
+        F = self._check_io(llr, info, ok, None, torch.float32)
+        _check_tensor("soft", soft, torch.float32, (F, self.N), self.device)
+        _check_tensor("trials", trials, torch.uint8, (F,), self.device)
+        _check(lib().pcg_decode_fsscan_f32(self._h, _ptr(llr), F, _ptr(info), _ptr(ok), _ptr(soft), _ptr(trials),
+                                           _stream(stream, llr)))
 
 
 class Puncturer:

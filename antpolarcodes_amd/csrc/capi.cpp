@@ -5,6 +5,7 @@
 #include "kernels.hpp"
 #include "plan.hpp"
 #include "rtc.hpp"
+#include "fsscan.hpp"
 #include "scan.hpp"
 
 #include <hip/hip_runtime.h>
@@ -91,8 +92,17 @@ struct pcg_plan {
     // SCAN plans (pcg_plan_create_scan; scan.hpp): host.ops holds ScanOp words, host.L = 1
     bool scan = false;
     uint32_t scan_iters = 0;
-    float* d_ext = nullptr;       // pcg_decode_scan_f32_host: extrinsic staging
+    void* d_ext = nullptr;        // pcg_decode_scan_f32_host: extrinsic staging (floats)
     uint64_t ext_frames = 0;
+    // Fast-SSCAN plans (pcg_plan_create_fsscan; fsscan.hpp): host.ops holds FsscanOp words
+    bool fsscan = false;
+    uint32_t fss_trials = 1;      // trial limit
+    int fss_forced = 0;           // run exactly fss_trials passes
+    uint32_t fss_slab = 0;        // floats of state per codeword
+    void* d_trials = nullptr;     // pcg_decode_fsscan_f32_host: trial-count staging (bytes)
+    uint64_t trials_frames = 0;
+    bool soft_plan() const { return scan || fsscan; } // SCAN or Fast-SSCAN: no rtc, no 8-bit, no puncturing
+    const char* soft_name() const { return fsscan ? "Fast-SSCAN" : "SCAN"; }
 };
 
 // The host-pointer pipeline of pcg_decode_f32_host / pcg_decode_i8_host: chunks of the
@@ -201,6 +211,7 @@ void free_plan_device(pcg_plan* p)
     }
     (void)hipFree(p->d_soft);
     (void)hipFree(p->d_ext);
+    (void)hipFree(p->d_trials);
     if (p->last_ev)
         (void)hipEventDestroy(p->last_ev);
     p->last_ev = nullptr;
@@ -232,7 +243,7 @@ constexpr uint64_t RTC_AUTO_FRAMES = 8192;
 // 8-bit lane-serial kernels, and both stages of adaptive plans; never with the op profiler.
 bool rtc_capable(const pcg_plan* p)
 {
-    if (p->dev_opprof || p->scan)
+    if (p->dev_opprof || p->soft_plan())
         return false;
     if (p->host.fixed) // the 8-bit lane-serial kernels (sccs, scl_char)
         return p->host.L > 1 || p->host.sc_kind == 0;
@@ -734,6 +745,8 @@ static int plan_finish(pcg_plan** out, pcg_plan* p, int device)
     // wave caps (hipOccupancy) of the lane-serial kernels, once per plan
     if (p->scan) {
         p->wave_cap = pcg::scan_wave_cap(h.N, h.systematic);
+    } else if (p->fsscan) {
+        p->wave_cap = pcg::fsscan_wave_cap(h.N, p->fss_slab);
     } else if (h.fixed && h.L == 1 && h.sc_kind == 0) {
         p->wave_cap = pcg::sccs_wave_cap(p->wave_lds_floats, false);
         p->wave_cap_i8 = pcg::sccs_wave_cap(p->wave_lds_floats, true);
@@ -880,9 +893,9 @@ int pcg_plan_describe(const pcg_plan* p, pcg_plan_desc* d)
         return fail(PCG_E_ARG, "null argument");
     d->block_length = p->host.N;
     d->info_length = p->host.K;
-    d->list_size = p->scan ? p->scan_iters : p->host.L;
+    d->list_size = p->scan ? p->scan_iters : p->fsscan ? p->fss_trials : p->host.L;
     d->node_count = p->host.node_count;
-    d->op_count = (uint32_t)p->host.ops.size();
+    d->op_count = (uint32_t)p->host.ops.size() / (p->fsscan ? pcg::FSS_WORDS : 1u);
     d->lds_bytes = p->wave_lds_floats * 4;
     d->scratch_bytes = p->scratch_floats * 4;
     d->crc_kind = p->host.crc_kind;
@@ -914,8 +927,8 @@ static int plan_specialize(pcg_plan* p, bool wait)
         if (rc != 0 || !rtc_capable(p))
             return rc;
     }
-    if (p->scan)
-        return fail(PCG_E_UNSUPPORTED, "no plan-specialised kernel for SCAN plans");
+    if (p->soft_plan())
+        return fail(PCG_E_UNSUPPORTED, std::string("no plan-specialised kernel for ") + p->soft_name() + " plans");
     if (!rtc_capable(p))
         return fail(PCG_E_UNSUPPORTED, "no plan-specialised kernel for this plan (not with PCG_OPPROF; the "
                                        "8-bit Fast-SSC decoder on its one-codeword-per-wave kernel has none)");
@@ -982,6 +995,43 @@ static int decode_scan(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info,
     return mark_done(p, s);
 }
 
+// FastSscanFloat::decode (fastsscan_float.cpp:309-339) over F frames: one launch of fsscan_kernel
+static int decode_fsscan(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info, uint8_t* ok, float* soft,
+                         uint8_t* trials, void* stream)
+{
+    const auto& h = p->host;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    pcg::FsscanArgs a{};
+    a.llr = llr;
+    a.F = F;
+    a.ops = p->d_ops;
+    a.nops = (uint32_t)h.ops.size() / pcg::FSS_WORDS;
+    a.N = h.N;
+    a.K = h.K;
+    a.kb = (h.K + 7) / 8;
+    a.trials = p->fss_trials;
+    a.forced = p->fss_forced;
+    a.info_pos = p->d_info_pos;
+    a.crc_c0 = h.crc_c0;
+    a.crc_bits = (uint32_t)h.crc_kind;
+    a.crc_rows = p->d_crc_m + h.crc_m.size();
+    a.info = info;
+    a.ok = ok;
+    a.soft = soft;
+    a.ntrials = trials;
+    a.slab_floats = p->fss_slab;
+    int rc = order_on(p, s);
+    if (rc != 0)
+        return rc;
+    a.units = (uint32_t)pcg::wave_units(F, 64, p->wave_cap);
+    if ((rc = grow_scratch(p, a.units, sizeof(float), s, 64ull * p->fss_slab)) != 0)
+        return rc;
+    a.slab = p->d_scratch;
+    if ((rc = pcg::launch_fsscan(a, s)) != 0)
+        return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return mark_done(p, s);
+}
+
 static int decode_adaptive(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info, uint8_t* ok, float* metrics,
                            void* stream, const int8_t* llr8 = nullptr)
 {
@@ -1034,6 +1084,8 @@ int pcg_decode_f32(pcg_plan* p,
     DeviceGuard g(p->device);
     if (p->scan) // info and ok only; there are no path metrics
         return decode_scan(p, llr, F, info, ok, nullptr, nullptr, stream);
+    if (p->fsscan)
+        return decode_fsscan(p, llr, F, info, ok, nullptr, nullptr, stream);
     if (p->fast)
         return decode_adaptive(p, llr, F, info, ok, metrics, stream);
     return decode_impl(p, llr, F, info, ok, metrics, stream, nullptr, nullptr);
@@ -1164,8 +1216,8 @@ int pcg_decode_i8(pcg_plan* p,
 {
     if (!p)
         return fail(PCG_E_ARG, "null plan");
-    if (p->scan)
-        return fail(PCG_E_UNSUPPORTED, "SCAN plans decode float LLRs only (no 8-bit SCAN)");
+    if (p->soft_plan())
+        return fail(PCG_E_UNSUPPORTED, std::string(p->soft_name()) + " plans decode float LLRs only (no 8-bit form)");
     if (!p->host.fixed)
         return fail(PCG_E_ARG, "int8 LLRs need an 8-bit plan (pcg_plan_create_char)");
     if (F == 0)
@@ -1538,8 +1590,8 @@ int pcg_decode_i8_host(pcg_plan* p, const int8_t* llr, uint64_t F, uint8_t* info
 {
     if (!p)
         return fail(PCG_E_ARG, "null plan");
-    if (p->scan)
-        return fail(PCG_E_UNSUPPORTED, "SCAN plans decode float LLRs only (no 8-bit SCAN)");
+    if (p->soft_plan())
+        return fail(PCG_E_UNSUPPORTED, std::string(p->soft_name()) + " plans decode float LLRs only (no 8-bit form)");
     if (!p->host.fixed)
         return fail(PCG_E_ARG, "int8 LLRs need an 8-bit plan (pcg_plan_create_char)");
     if (F == 0)
@@ -1564,6 +1616,8 @@ int pcg_decode_f32_host(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info
         return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
     if (p->scan)
         return pcg_decode_scan_f32_host(p, llr, F, info, ok, nullptr, nullptr);
+    if (p->fsscan)
+        return pcg_decode_fsscan_f32_host(p, llr, F, info, ok, nullptr, nullptr);
     DeviceGuard g(p->device);
     return decode_host(p, llr, sizeof(float), F, info, ok, metrics);
 }
@@ -1592,6 +1646,11 @@ int pcg_decode_f32_soft(pcg_plan* p,
             return fail(PCG_E_ARG, "null llr/info/soft buffer");
         return pcg_decode_scan_f32(p, llr, F, info, ok, soft, nullptr, stream);
     }
+    if (p && p->fsscan) {
+        if (F != 0 && !soft)
+            return fail(PCG_E_ARG, "null llr/info/soft buffer");
+        return pcg_decode_fsscan_f32(p, llr, F, info, ok, soft, nullptr, stream);
+    }
     int rc = soft_supported(p);
     if (rc != 0)
         return rc;
@@ -1613,6 +1672,11 @@ int pcg_decode_f32_soft_host(pcg_plan* p, const float* llr, uint64_t F, uint8_t*
         if (F != 0 && !soft)
             return fail(PCG_E_ARG, "null llr/info/soft buffer");
         return pcg_decode_scan_f32_host(p, llr, F, info, ok, soft, nullptr);
+    }
+    if (p && p->fsscan) {
+        if (F != 0 && !soft)
+            return fail(PCG_E_ARG, "null llr/info/soft buffer");
+        return pcg_decode_fsscan_f32_host(p, llr, F, info, ok, soft, nullptr);
     }
     int rc = soft_supported(p);
     if (rc != 0)
@@ -1683,9 +1747,10 @@ int pcg_decode_punctured_f32(pcg_plan* p,
 {
     if (!p || !punc)
         return fail(PCG_E_ARG, "null plan/puncturer");
-    if (p->scan)
-        return fail(PCG_E_UNSUPPORTED, "SCAN plans do not decode punctured frames (depuncture with "
-                                       "pcg_depuncture_f32, then pcg_decode_scan_f32)");
+    if (p->soft_plan())
+        return fail(PCG_E_UNSUPPORTED, std::string(p->soft_name()) +
+                                           " plans do not decode punctured frames (depuncture with "
+                                           "pcg_depuncture_f32, then decode)");
     if (punc->N != p->host.N)
         return fail(PCG_E_ARG, "puncturer parent length != decoder block length");
     if (F == 0)
@@ -1802,6 +1867,78 @@ int pcg_decode_scan_f32(pcg_plan* p,
     return decode_scan(p, llr, F, info, ok, soft, extrinsic, stream);
 }
 
+// The host-pointer pipeline of the soft-output plans (SCAN, Fast-SSCAN): chunks of
+// pcg_decode_f32_host's size (PCG_HOST_CHUNK overrides it) through staging kept in the plan; the
+// null-stream copies are ordered after the plan's previous decode.  `extra` is the plan's fourth
+// output (extrinsic information / trial counts), xbytes per frame, staged in d_extra (capacity
+// xframes frames); decode(n, d_extra or null) launches n frames from p->d_llr into the staging.
+extern "C++" {
+template <typename Decode>
+static int soft_decode_host(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info, uint8_t* ok, float* soft,
+                            void* extra, uint64_t xbytes, void*& d_extra, uint64_t& xframes, const char* xwhat,
+                            Decode decode)
+{
+    const uint64_t N = p->host.N, kb = (p->host.K + 7) / 8;
+    uint64_t chunk = (uint64_t)env_int("PCG_HOST_CHUNK", 0);
+    if (chunk == 0)
+        chunk = std::min<uint64_t>(65536, std::max<uint64_t>(4096, (64ull << 20) / (N * sizeof(float))));
+    chunk = std::min<uint64_t>(chunk, F);
+    int rc = order_on(p, nullptr);
+    if (rc != 0)
+        return rc;
+    hipError_t e;
+    if (p->stage_frames < chunk || (soft && p->soft_frames < chunk) || (extra && xframes < chunk)) {
+        if ((e = hipStreamSynchronize(nullptr)) != hipSuccess)
+            return hip_fail(e, "hipStreamSynchronize");
+    }
+    if (p->stage_frames < chunk) {
+        (void)hipFree(p->d_llr);
+        (void)hipFree(p->d_info);
+        (void)hipFree(p->d_ok);
+        p->d_llr = nullptr;
+        p->d_info = nullptr;
+        p->d_ok = nullptr;
+        p->stage_frames = 0;
+        if ((e = hipMalloc(&p->d_llr, chunk * N * sizeof(float))) != hipSuccess ||
+            (e = hipMalloc(&p->d_info, chunk * std::max<uint64_t>(kb, 1))) != hipSuccess ||
+            (e = hipMalloc(&p->d_ok, chunk)) != hipSuccess)
+            return hip_fail(e, "hipMalloc(soft-output staging)");
+        p->stage_frames = chunk;
+    }
+    if (soft && p->soft_frames < chunk) {
+        (void)hipFree(p->d_soft);
+        p->d_soft = nullptr;
+        p->soft_frames = 0;
+        if ((e = hipMalloc(&p->d_soft, chunk * N * sizeof(float))) != hipSuccess)
+            return hip_fail(e, "hipMalloc(soft codewords)");
+        p->soft_frames = chunk;
+    }
+    if (extra && xframes < chunk) {
+        (void)hipFree(d_extra);
+        d_extra = nullptr;
+        xframes = 0;
+        if ((e = hipMalloc(&d_extra, chunk * xbytes)) != hipSuccess)
+            return hip_fail(e, xwhat);
+        xframes = chunk;
+    }
+    for (uint64_t f0 = 0; f0 < F; f0 += chunk) {
+        const uint64_t n = std::min(chunk, F - f0);
+        if ((e = hipMemcpy(p->d_llr, llr + f0 * N, n * N * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
+            return hip_fail(e, "hipMemcpy(H2D)");
+        if ((rc = decode(n, extra ? d_extra : nullptr)) != 0)
+            return rc;
+        if ((kb && (e = hipMemcpy(info + f0 * kb, p->d_info, n * kb, hipMemcpyDeviceToHost)) != hipSuccess) ||
+            (ok && (e = hipMemcpy(ok + f0, p->d_ok, n, hipMemcpyDeviceToHost)) != hipSuccess) ||
+            (soft && (e = hipMemcpy(soft + f0 * N, p->d_soft, n * N * sizeof(float), hipMemcpyDeviceToHost)) !=
+                         hipSuccess) ||
+            (extra && (e = hipMemcpy(static_cast<uint8_t*>(extra) + f0 * xbytes, d_extra, n * xbytes,
+                                     hipMemcpyDeviceToHost)) != hipSuccess))
+            return hip_fail(e, "hipMemcpy(D2H)");
+    }
+    return PCG_OK;
+}
+} // extern "C++"
+
 int pcg_decode_scan_f32_host(pcg_plan* p,
                              const float* llr,
                              uint64_t F,
@@ -1821,67 +1958,106 @@ int pcg_decode_scan_f32_host(pcg_plan* p,
     if (p->device < 0)
         return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
     DeviceGuard g(p->device);
-    const uint64_t N = p->host.N, kb = (p->host.K + 7) / 8;
-    // chunks of pcg_decode_f32_host's size (PCG_HOST_CHUNK overrides it), through staging kept
-    // in the plan; the null-stream copies are ordered after the plan's previous decode
-    uint64_t chunk = (uint64_t)env_int("PCG_HOST_CHUNK", 0);
-    if (chunk == 0)
-        chunk = std::min<uint64_t>(65536, std::max<uint64_t>(4096, (64ull << 20) / (N * sizeof(float))));
-    chunk = std::min<uint64_t>(chunk, F);
-    int rc = order_on(p, nullptr);
-    if (rc != 0)
-        return rc;
-    hipError_t e;
-    if (p->stage_frames < chunk || (soft && p->soft_frames < chunk) || (extrinsic && p->ext_frames < chunk)) {
-        if ((e = hipStreamSynchronize(nullptr)) != hipSuccess)
-            return hip_fail(e, "hipStreamSynchronize");
+    return soft_decode_host(p, llr, F, info, ok, soft, extrinsic, p->host.N * sizeof(float), p->d_ext, p->ext_frames,
+                            "hipMalloc(extrinsic information)", [&](uint64_t n, void* d_x) {
+                                return decode_scan(p, p->d_llr, n, p->d_info, ok ? p->d_ok : nullptr,
+                                                   soft ? p->d_soft : nullptr, static_cast<float*>(d_x), nullptr);
+                            });
+}
+
+int pcg_plan_create_fsscan(pcg_plan** out,
+                           uint32_t N,
+                           uint32_t trial_limit,
+                           const uint32_t* frozen,
+                           uint32_t n_frozen,
+                           int systematic,
+                           int crc_kind,
+                           int device)
+{
+    if (!out)
+        return fail(PCG_E_ARG, "plan output pointer is null");
+    *out = nullptr;
+    if (trial_limit < 1 || trial_limit > 255)
+        return fail(PCG_E_ARG, "Fast-SSCAN: the trial limit must be in [1, 255]");
+    auto* p = new pcg_plan();
+    std::string err;
+    const int rc = pcg::build_fsscan_plan(p->host, N, frozen, n_frozen, systematic, crc_kind, &p->fss_slab, &err);
+    if (rc != 0) {
+        delete p;
+        return fail(rc, err);
     }
-    if (p->stage_frames < chunk) {
-        (void)hipFree(p->d_llr);
-        (void)hipFree(p->d_info);
-        (void)hipFree(p->d_ok);
-        p->d_llr = nullptr;
-        p->d_info = nullptr;
-        p->d_ok = nullptr;
-        p->stage_frames = 0;
-        if ((e = hipMalloc(&p->d_llr, chunk * N * sizeof(float))) != hipSuccess ||
-            (e = hipMalloc(&p->d_info, chunk * std::max<uint64_t>(kb, 1))) != hipSuccess ||
-            (e = hipMalloc(&p->d_ok, chunk)) != hipSuccess)
-            return hip_fail(e, "hipMalloc(scan staging)");
-        p->stage_frames = chunk;
-    }
-    if (soft && p->soft_frames < chunk) {
-        (void)hipFree(p->d_soft);
-        p->d_soft = nullptr;
-        p->soft_frames = 0;
-        if ((e = hipMalloc(&p->d_soft, chunk * N * sizeof(float))) != hipSuccess)
-            return hip_fail(e, "hipMalloc(soft codewords)");
-        p->soft_frames = chunk;
-    }
-    if (extrinsic && p->ext_frames < chunk) {
-        (void)hipFree(p->d_ext);
-        p->d_ext = nullptr;
-        p->ext_frames = 0;
-        if ((e = hipMalloc(&p->d_ext, chunk * N * sizeof(float))) != hipSuccess)
-            return hip_fail(e, "hipMalloc(extrinsic information)");
-        p->ext_frames = chunk;
-    }
-    for (uint64_t f0 = 0; f0 < F; f0 += chunk) {
-        const uint64_t n = std::min(chunk, F - f0);
-        if ((e = hipMemcpy(p->d_llr, llr + f0 * N, n * N * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
-            return hip_fail(e, "hipMemcpy(H2D)");
-        if ((rc = decode_scan(p, p->d_llr, n, p->d_info, ok ? p->d_ok : nullptr, soft ? p->d_soft : nullptr,
-                              extrinsic ? p->d_ext : nullptr, nullptr)) != 0)
-            return rc;
-        if ((e = hipMemcpy(info + f0 * kb, p->d_info, n * kb, hipMemcpyDeviceToHost)) != hipSuccess ||
-            (ok && (e = hipMemcpy(ok + f0, p->d_ok, n, hipMemcpyDeviceToHost)) != hipSuccess) ||
-            (soft && (e = hipMemcpy(soft + f0 * N, p->d_soft, n * N * sizeof(float), hipMemcpyDeviceToHost)) !=
-                         hipSuccess) ||
-            (extrinsic && (e = hipMemcpy(extrinsic + f0 * N, p->d_ext, n * N * sizeof(float),
-                                         hipMemcpyDeviceToHost)) != hipSuccess))
-            return hip_fail(e, "hipMemcpy(D2H)");
-    }
+    p->fsscan = true;
+    p->fss_trials = trial_limit;
+    p->host.sc_kind = 0;
+    p->rtc_mode = 0;
+    p->kernel = "fsscan_kernel";
+    p->wave_lds_floats = pcg::fsscan_lds_bytes(N) / 4u;
+    p->scratch_floats = p->fss_slab; // per codeword
+    return plan_finish(out, p, device);
+}
+
+int pcg_plan_set_fsscan_trials(pcg_plan* p, uint32_t trial_limit, int forced)
+{
+    if (!p)
+        return fail(PCG_E_ARG, "null plan");
+    if (!p->fsscan)
+        return fail(PCG_E_ARG, "not a Fast-SSCAN plan (pcg_plan_create_fsscan)");
+    if (trial_limit < 1 || trial_limit > 255)
+        return fail(PCG_E_ARG, "Fast-SSCAN: the trial limit must be in [1, 255]");
+    p->fss_trials = trial_limit;
+    p->fss_forced = forced ? 1 : 0;
     return PCG_OK;
+}
+
+int pcg_decode_fsscan_f32(pcg_plan* p,
+                          const float* llr,
+                          uint64_t F,
+                          uint8_t* info,
+                          uint8_t* ok,
+                          float* soft,
+                          uint8_t* trials,
+                          void* stream)
+{
+    if (!p)
+        return fail(PCG_E_ARG, "null plan");
+    if (!p->fsscan)
+        return fail(PCG_E_ARG, "not a Fast-SSCAN plan (pcg_plan_create_fsscan)");
+    if (F == 0)
+        return PCG_OK;
+    if (!llr || !info)
+        return fail(PCG_E_ARG, "null llr/info buffer");
+    if (p->device < 0)
+        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
+    if (F > 0xFFFFFFFFull)
+        return fail(PCG_E_ARG, "at most 2^32 - 1 frames per call");
+    DeviceGuard g(p->device);
+    return decode_fsscan(p, llr, F, info, ok, soft, trials, stream);
+}
+
+int pcg_decode_fsscan_f32_host(pcg_plan* p,
+                               const float* llr,
+                               uint64_t F,
+                               uint8_t* info,
+                               uint8_t* ok,
+                               float* soft,
+                               uint8_t* trials)
+{
+    if (!p)
+        return fail(PCG_E_ARG, "null plan");
+    if (!p->fsscan)
+        return fail(PCG_E_ARG, "not a Fast-SSCAN plan (pcg_plan_create_fsscan)");
+    if (F == 0)
+        return PCG_OK;
+    if (!llr || !info)
+        return fail(PCG_E_ARG, "null llr/info buffer");
+    if (p->device < 0)
+        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
+    DeviceGuard g(p->device);
+    return soft_decode_host(p, llr, F, info, ok, soft, trials, 1, p->d_trials, p->trials_frames,
+                            "hipMalloc(trial counts)", [&](uint64_t n, void* d_x) {
+                                return decode_fsscan(p, p->d_llr, n, p->d_info, ok ? p->d_ok : nullptr,
+                                                     soft ? p->d_soft : nullptr, static_cast<uint8_t*>(d_x), nullptr);
+                            });
 }
 
 void pcg_plan_destroy(pcg_plan* p)

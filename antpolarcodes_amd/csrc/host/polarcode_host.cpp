@@ -3,6 +3,7 @@
 // top of the C ABI (include/pcg.h).  No device code here.
 #include <polarcode/construction/constructor.h>
 #include <polarcode/decoding/decoder.h>
+#include <polarcode/decoding/fastsscan_float.h>
 #include <polarcode/decoding/scan.h>
 #include <polarcode/encoding/butterfly_fip_packed.h>
 #include <polarcode/encoding/encoder.h>
@@ -1012,6 +1013,146 @@ void Scan::decodeBatchSoftDevice(const float* llr, size_t F, uint8_t* info, uint
 }
 
 void Scan::decodeBatchDevice(const float* llr, size_t F, uint8_t* info, uint8_t* ok, float*, void* hipStream)
+{
+    decodeBatchSoftDevice(llr, F, info, ok, nullptr, nullptr, hipStream);
+}
+
+// ---- FastSscanFloat (fastsscan_float.cpp): SCAN with closed-form subtrees and detector-terminated
+// passes on the GPU -------------------------------------------------------------------------------
+FastSscanFloat::FastSscanFloat(size_t blockLength, unsigned trialLimit, const std::vector<unsigned>& frozenBits,
+                               int device)
+    : mTrialLimit(trialLimit), mDevice(device)
+{
+    initialize(blockLength, trialLimit, frozenBits);
+}
+
+FastSscanFloat::~FastSscanFloat() { releasePlan(); }
+
+void FastSscanFloat::releasePlan()
+{
+    if (mPlan)
+        pcg_plan_destroy(mPlan);
+    mPlan = nullptr;
+}
+
+// fastsscan_float.cpp:288-307: float input and output containers, the packed output bytes
+void FastSscanFloat::initialize(size_t blockLength, unsigned trialLimit, const std::vector<unsigned>& frozenBits)
+{
+    Decoder::initialize(blockLength, frozenBits);
+    mTrialLimit = trialLimit;
+    mPasses = 0;
+    releasePlan();
+    pcg_plan* probe = nullptr; // validate now, without a GPU
+    const int rc = pcg_plan_create_fsscan(&probe, (uint32_t)blockLength, trialLimit, mFrozenBits.data(),
+                                          (uint32_t)mFrozenBits.size(), 1, 0, -1);
+    if (rc != 0)
+        throw_pcg(rc);
+    pcg_plan_destroy(probe);
+    if (!mExternalContainers) {
+        delete mLlrContainer;
+        delete mBitContainer;
+        delete[] mOutputContainer;
+    }
+    mExternalContainers = false;
+    mLlrContainer = new FloatContainer(mBlockLength, mFrozenBits);
+    mBitContainer = new FloatContainer(mBlockLength, mFrozenBits);
+    mOutputContainer = new unsigned char[(mBlockLength + 7) / 8]();
+}
+
+void FastSscanFloat::setTrialLimit(unsigned trialLimit)
+{
+    if (trialLimit < 1 || trialLimit > 255)
+        throw std::logic_error("Fast-SSCAN: the trial limit must be in [1, 255]");
+    mTrialLimit = trialLimit;
+}
+
+void FastSscanFloat::setErrorDetection(ErrorDetection::Detector* pDetector)
+{
+    if (ErrorDetection::gpuKind(pDetector) < 0)
+        throw std::logic_error("detector " + pDetector->getType() + " cannot be evaluated on the GPU");
+    mErrorDetector = pDetector;
+}
+
+void FastSscanFloat::ensurePlan()
+{
+    const int kind = ErrorDetection::gpuKind(mErrorDetector);
+    if (mPlan && kind == mPlanKind)
+        return;
+    releasePlan();
+    const int rc = pcg_plan_create_fsscan(&mPlan, (uint32_t)mBlockLength, mTrialLimit, mFrozenBits.data(),
+                                          (uint32_t)mFrozenBits.size(), mSystematic ? 1 : 0, kind, mDevice);
+    if (rc != 0) {
+        mPlan = nullptr;
+        throw_pcg(rc);
+    }
+    mPlanKind = kind;
+}
+
+bool FastSscanFloat::run(unsigned trials, bool forced)
+{
+    ensurePlan();
+    int rc = pcg_plan_set_fsscan_trials(mPlan, trials, forced ? 1 : 0);
+    if (rc != 0)
+        throw_pcg(rc);
+    uint8_t ok = 0, passes = 0;
+    rc = pcg_decode_fsscan_f32_host(mPlan, static_cast<FloatContainer*>(mLlrContainer)->data(), 1, mOutputContainer,
+                                    &ok, static_cast<FloatContainer*>(mBitContainer)->data(), &passes);
+    if (rc != 0)
+        throw_pcg(rc);
+    mPasses = passes;
+    return ok != 0;
+}
+
+bool FastSscanFloat::decode() { return run(mTrialLimit, false); }
+
+bool FastSscanFloat::decodeAgain()
+{
+    if (mPasses == 0)
+        throw std::logic_error("decodeAgain() needs a decode() before it");
+    if (mPasses >= 255)
+        throw std::logic_error("Fast-SSCAN: at most 255 passes per frame");
+    return run(mPasses + 1, true);
+}
+
+bool FastSscanFloat::decodeBatchSoft(const float* llr, size_t F, uint8_t* info, uint8_t* ok, float* soft,
+                                     uint8_t* trials)
+{
+    ensurePlan();
+    std::vector<uint8_t> okv;
+    uint8_t* okp = ok;
+    if (!okp) {
+        okv.assign(F, 0);
+        okp = okv.data();
+    }
+    int rc = pcg_plan_set_fsscan_trials(mPlan, mTrialLimit, 0);
+    if (rc == 0)
+        rc = pcg_decode_fsscan_f32_host(mPlan, llr, F, info, okp, soft, trials);
+    if (rc != 0)
+        throw_pcg(rc);
+    for (size_t f = 0; f < F; ++f)
+        if (!okp[f])
+            return false;
+    return true;
+}
+
+bool FastSscanFloat::decodeBatch(const float* llr, size_t F, uint8_t* info, uint8_t* ok, float*)
+{
+    return decodeBatchSoft(llr, F, info, ok, nullptr, nullptr);
+}
+
+void FastSscanFloat::decodeBatchSoftDevice(const float* llr, size_t F, uint8_t* info, uint8_t* ok, float* soft,
+                                           uint8_t* trials, void* hipStream)
+{
+    ensurePlan();
+    int rc = pcg_plan_set_fsscan_trials(mPlan, mTrialLimit, 0);
+    if (rc == 0)
+        rc = pcg_decode_fsscan_f32(mPlan, llr, F, info, ok, soft, trials, hipStream);
+    if (rc != 0)
+        throw_pcg(rc);
+}
+
+void FastSscanFloat::decodeBatchDevice(const float* llr, size_t F, uint8_t* info, uint8_t* ok, float*,
+                                       void* hipStream)
 {
     decodeBatchSoftDevice(llr, F, info, ok, nullptr, nullptr, hipStream);
 }

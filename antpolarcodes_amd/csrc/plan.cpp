@@ -2,6 +2,7 @@
 #include "plan.hpp"
 
 #include "crc_host.hpp"
+#include "fsscan.hpp"
 #include "scan.hpp"
 
 #include <cstdlib>
@@ -380,6 +381,66 @@ void scan_emit(PlanHost& p, const std::vector<uint32_t>& f, uint32_t n, uint32_t
     p.ops.push_back(mkscan(SCAN_UP, level, group, fl));
 }
 
+// FastSscanFloat (fastsscan_float.cpp) in decode order.  createDecoder's node kinds in its order
+// (:238-265); a RateR node is its three phases around its children (RateRNode::decode :116-163),
+// a Repetition or TwoBit node one op, a Zero or One node none: its constant message is a flag on
+// its parent's ops, and the phase that would compute its input is not emitted.  `own` is where
+// the node's message goes (the root's and a left child's in EL of their level, a right child's
+// in a slot of its own after EL, assigned here); *er_top is the next free slot.
+int fsscan_kind(const std::vector<uint32_t>& f, uint32_t n)
+{
+    if (f.size() == n)
+        return FSS_NODE_ZERO;
+    if (f.empty())
+        return FSS_NODE_ONE;
+    if (n == 2)
+        return FSS_NODE_TWO;
+    if (f.size() == n - 1)
+        return FSS_NODE_REP;
+    return FSS_NODE_RATER;
+}
+
+void fsscan_emit(PlanHost& p, const std::vector<uint32_t>& f, uint32_t n, uint32_t level, uint32_t group,
+                 uint32_t own, uint32_t* er_top)
+{
+    const int kind = fsscan_kind(f, n);
+    p.node_count++;
+    p.node_types.push_back(kind);
+    auto push = [&](uint32_t code, uint32_t fl, uint32_t er) {
+        p.ops.push_back(mkscan(code, level, group, fl));
+        p.ops.push_back(er);
+        p.ops.push_back(own);
+    };
+    if (kind == FSS_NODE_ZERO || kind == FSS_NODE_ONE) {
+        if (level == 0) // the root: its message is written once per pass for the output
+            push(FSS_CONST, kind == FSS_NODE_ZERO ? FSS_L_ZERO : FSS_L_ONE, 0);
+        return;
+    }
+    if (kind == FSS_NODE_TWO || kind == FSS_NODE_REP) {
+        push(kind == FSS_NODE_TWO ? FSS_TWO : FSS_REP, 0, 0);
+        return;
+    }
+    const uint32_t h = n / 2;
+    std::vector<uint32_t> lf, rf;
+    split(f, h, lf, rf);
+    const int lk = fsscan_kind(lf, h), rk = fsscan_kind(rf, h);
+    const bool lc = lk == FSS_NODE_ZERO || lk == FSS_NODE_ONE, rc = rk == FSS_NODE_ZERO || rk == FSS_NODE_ONE;
+    const uint32_t fl = (lk == FSS_NODE_ZERO ? FSS_L_ZERO : 0u) | (lk == FSS_NODE_ONE ? FSS_L_ONE : 0u) |
+                        (rk == FSS_NODE_ZERO ? FSS_R_ZERO : 0u) | (rk == FSS_NODE_ONE ? FSS_R_ONE : 0u);
+    uint32_t er = 0;
+    if (!rc) {
+        er = *er_top;
+        *er_top += (h + 3u) & ~3u;
+    }
+    if (!lc)
+        push(FSS_LEFT, fl, er);
+    fsscan_emit(p, lf, h, level + 1, 2 * group, fsscan_el(p.N) + fsscan_lvl(p.N, level + 1), er_top);
+    if (!rc)
+        push(FSS_RIGHT, fl, er);
+    fsscan_emit(p, rf, h, level + 1, 2 * group + 1, er, er_top);
+    push(FSS_OUT, fl, er);
+}
+
 int build_impl(PlanHost& p,
                uint32_t N,
                uint32_t L,
@@ -389,15 +450,17 @@ int build_impl(PlanHost& p,
                int crc_kind,
                std::string* err,
                int fixed,
-               int scan)
+               int scan, // 1 = SCAN, 2 = Fast-SSCAN
+               uint32_t* slab_floats = nullptr)
 {
     p = PlanHost();
+    const std::string who = scan == 2 ? "Fast-SSCAN" : "SCAN";
     if (scan && (N < 8 || (N & (N - 1)))) {
-        *err = "SCAN: block length must be a power of two >= 8";
+        *err = who + ": block length must be a power of two >= 8";
         return -1;
     }
     if (scan && N > SCAN_MAX_N) {
-        *err = "SCAN: block lengths above " + std::to_string(SCAN_MAX_N) + " are not supported";
+        *err = who + ": block lengths above " + std::to_string(SCAN_MAX_N) + " are not supported";
         return -4;
     }
     // Fast-SSC float plans run codes down to N = 2 (the reference's own Repetition /
@@ -442,7 +505,11 @@ int build_impl(PlanHost& p,
         p.sc_kind = (k && std::string(k) == "wave") ? 1 : ((k && std::string(k) == "scs") ? 0 : 2);
     }
     try {
-        if (scan)
+        if (scan == 2) {
+            uint32_t top = fsscan_er(N);
+            fsscan_emit(p, p.frozen, N, 0, 0, fsscan_el(N), &top);
+            *slab_floats = top;
+        } else if (scan)
             scan_emit(p, p.frozen, N, 0, 0);
         else if (p.fixed && L == 1)
             sc_char_emit(p, p.frozen, N, 0);
@@ -547,6 +614,18 @@ int build_scan_plan(PlanHost& p,
                     std::string* err)
 {
     return build_impl(p, N, 1, frozen, nf, systematic, crc_kind, err, 0, 1);
+}
+
+int build_fsscan_plan(PlanHost& p,
+                      uint32_t N,
+                      const uint32_t* frozen,
+                      uint32_t nf,
+                      int systematic,
+                      int crc_kind,
+                      uint32_t* slab_floats,
+                      std::string* err)
+{
+    return build_impl(p, N, 1, frozen, nf, systematic, crc_kind, err, 0, 2, slab_floats);
 }
 
 } // namespace pcg

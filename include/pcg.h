@@ -35,6 +35,11 @@
  *   pcg_decode_scan_f32[_host] <- Scan::decode scan.cpp:223-297 (updatellrmap :80-126,
  *                        updatebitmap :128-210), Decoder::getSoftCodeword, and
  *                        Scan::getExtrinsicChannelInformation scan.cpp:299-304, batched
+ *   pcg_plan_create_fsscan <- new Decoding::FastSscanFloat(N, trialLimit, frozen)
+ *                        (src/polarcode/decoding/fastsscan_float.cpp:269-307, createDecoder :238-265)
+ *   pcg_plan_set_fsscan_trials <- the trial limit; forced passes serve decodeAgain :320-325
+ *   pcg_decode_fsscan_f32[_host] <- FastSscanFloat::decode :309-339 (RateRNode::decode :116-163,
+ *                        RepetitionNode :202-223, TwoBitNode :231-235), batched
  *   pcg_plan_destroy  <- Decoder::~Decoder decoder.cpp:104-114
  *   pcg_last_error    <- the std::exception text the reference throws
  *   pcg_puncturer_*   <- PolarCode::Puncturer (include/polarcode/puncturer.h:33-99,
@@ -296,6 +301,59 @@ int pcg_decode_scan_f32_host(pcg_plan* plan,
                              uint8_t* ok,
                              float* soft,
                              float* extrinsic);
+
+/* ---- Fast-SSCAN: SCAN with closed-form subtrees and detector-terminated passes ------------
+ * (Decoding::FastSscanFloat, fastsscan_float.cpp.)  The same factor graph as SCAN in natural
+ * index order; rate-0, rate-1, repetition and size-2 subtrees are closed forms, and a pass is
+ * repeated only while the frame's detector check fails, up to trial_limit (1 .. 255; 0 is
+ * PCG_E_ARG: the reference would return stale output).  Outputs equal the reference's bit for
+ * bit: the soft codeword (channel LLR + root message), the info bytes (its sign bits at the
+ * information positions) and ok; `trials` is the number of passes each frame ran.  With the
+ * dummy detector (crc_kind 0) every frame stops after pass 1.  Frames are independent: every
+ * frame starts from reset() state -- also the message of a right-child TwoBit node, which a
+ * reused reference instance carries over from its previous frame.
+ * `systematic` is recorded for pcg_plan_describe and otherwise ignored, as in the reference.
+ * Contract: finite LLRs whose sums stay finite.  N: a power of two, 8 <= N <= 4096
+ * (PCG_E_UNSUPPORTED above); any strictly ascending frozen set.  pcg_plan_describe reports
+ * list_size = trial_limit, lds_bytes of a wave and scratch_bytes per codeword;
+ * pcg_plan_kernel_name is "fsscan_kernel".  pcg_decode_f32[_host] and pcg_decode_f32_soft[_host]
+ * work as on a SCAN plan; pcg_plan_specialize[_async], pcg_decode_i8[_host] and
+ * pcg_decode_punctured_f32 return PCG_E_UNSUPPORTED, pcg_decode_scan_f32[_host] PCG_E_ARG. */
+int pcg_plan_create_fsscan(pcg_plan** plan,
+                           uint32_t N,
+                           uint32_t trial_limit,
+                           const uint32_t* frozen,
+                           uint32_t n_frozen,
+                           int systematic,
+                           int crc_kind,
+                           int device);
+
+/* The trial limit (1 .. 255) of later decodes.  forced != 0: run exactly trial_limit passes and
+ * ignore the check in between; ok is the check after the last pass (FastSscanFloat::decodeAgain
+ * after t passes = t + 1 forced passes; fixed-pass soft output with the dummy detector). */
+int pcg_plan_set_fsscan_trials(pcg_plan* plan, uint32_t trial_limit, int forced);
+
+/* Decode F frames with a Fast-SSCAN plan (PCG_E_ARG for any other plan).  Device pointers,
+ * asynchronous, stream-ordered like pcg_decode_f32.  info: F x ceil(K/8) bytes.  ok (F bytes),
+ * soft (F x N floats, natural order) and trials (F bytes) may be NULL: an output not asked for
+ * costs no stores. */
+int pcg_decode_fsscan_f32(pcg_plan* plan,
+                          const float* llr,
+                          uint64_t F,
+                          uint8_t* info,
+                          uint8_t* ok,
+                          float* soft,
+                          uint8_t* trials,
+                          void* stream);
+
+/* Same with HOST pointers; synchronous.  Streams the batch through device buffers in chunks. */
+int pcg_decode_fsscan_f32_host(pcg_plan* plan,
+                               const float* llr,
+                               uint64_t F,
+                               uint8_t* info,
+                               uint8_t* ok,
+                               float* soft,
+                               uint8_t* trials);
 
 int pcg_plan_describe(const pcg_plan* plan, pcg_plan_desc* desc);
 
