@@ -92,6 +92,10 @@ def lib():
         L.pcg_plan_set_fsscan_trials.argtypes = [P, C.c_uint32, C.c_int]
         L.pcg_decode_fsscan_f32.argtypes = [P, P, C.c_uint64, P, P, P, P, P]
         L.pcg_decode_fsscan_f32_host.argtypes = [P, P, C.c_uint64, P, P, P, P]
+        L.pcg_plan_create_depthfirst.argtypes = L.pcg_plan_create.argtypes
+        L.pcg_plan_set_depthfirst_trials.argtypes = [P, C.c_uint32]
+        L.pcg_decode_depthfirst_f32.argtypes = [P, P, C.c_uint64, P, P, P, P, P]
+        L.pcg_decode_depthfirst_f32_host.argtypes = [P, P, C.c_uint64, P, P, P, P]
         L.pcg_plan_describe.argtypes = [P, C.POINTER(PlanDesc)]
         L.pcg_plan_kernel_name.argtypes = [P]
         L.pcg_plan_kernel_name.restype = C.c_char_p
@@ -390,6 +394,55 @@ class FastSscanPlan(Plan):
         _check_tensor("trials", trials, torch.uint8, (F,), self.device)
         _check(lib().pcg_decode_fsscan_f32(self._h, _ptr(llr), F, _ptr(info), _ptr(ok), _ptr(soft), _ptr(trials),
                                            _stream(stream, llr)))
+
+
+class DepthFirstPlan(Plan):
+    """An SC-Flip plan (pcg_plan_create_depthfirst): the reference's Decoding::DepthFirst, plain
+    successive cancellation repeated with the least reliable information-bit decisions flipped
+    while the frame's detector check fails, up to `trials` decodes.  Returns info, ok, the decoded
+    codeword words (F x N uint32, what getSoftCodeword returns) and the trials run per frame
+    (uint8)."""
+
+    def __init__(self, N, trials, frozen, systematic=True, crc=8, device=0):
+        fr, fp = _frozen_array(frozen)
+        h = C.c_void_p()
+        _check(lib().pcg_plan_create_depthfirst(C.byref(h), int(N), int(trials), fp, int(fr.size),
+                                                int(bool(systematic)), int(crc), int(device)))
+        self._h = h
+        self.N, self.L, self.K = int(N), 1, int(N) - int(fr.size)
+        self.trials = int(trials)
+        self.kb = (self.K + 7) // 8
+        self.device = device
+        self.fixed = False
+
+    def set_trials(self, trials):
+        """The trial limit of later decodes (pcg_plan_set_depthfirst_trials)."""
+        _check(lib().pcg_plan_set_depthfirst_trials(self._h, int(trials)))
+        self.trials = int(trials)
+
+    def decode_host(self, llr, want_ok=True, want_bits=True, want_trials=True):
+        """Host arrays: returns (info, ok, bits, trials) (pcg_decode_depthfirst_f32_host); an
+        output not asked for is None."""
+        llr = np.ascontiguousarray(llr, dtype=np.float32).reshape(-1, self.N)
+        F = llr.shape[0]
+        info = np.zeros((F, self.kb), np.uint8)
+        ok = np.zeros(F, np.uint8) if want_ok else None
+        bits = np.zeros((F, self.N), np.uint32) if want_bits else None
+        trials = np.zeros(F, np.uint8) if want_trials else None
+        _check(lib().pcg_decode_depthfirst_f32_host(self._h, llr.ctypes.data, F, info.ctypes.data,
+                                                    *(None if a is None else a.ctypes.data
+                                                      for a in (ok, bits, trials))))
+        return info, ok, bits, trials
+
+    def decode_device(self, llr, info, ok=None, bits=None, trials=None, stream=None):
+        """Device-resident decode of torch CUDA tensors (pcg_decode_depthfirst_f32): llr float32
+        F x N, info uint8 F x ceil(K/8), ok and trials uint8 F, bits int32 F x N (each or None)."""
+        import torch
+        F = self._check_io(llr, info, ok, None, torch.float32)
+        _check_tensor("bits", bits, torch.int32, (F, self.N), self.device)
+        _check_tensor("trials", trials, torch.uint8, (F,), self.device)
+        _check(lib().pcg_decode_depthfirst_f32(self._h, _ptr(llr), F, _ptr(info), _ptr(ok), _ptr(bits),
+                                               _ptr(trials), _stream(stream, llr)))
 
 
 class Puncturer:

@@ -5,6 +5,7 @@
 #include "kernels.hpp"
 #include "plan.hpp"
 #include "rtc.hpp"
+#include "depthfirst.hpp"
 #include "fsscan.hpp"
 #include "scan.hpp"
 
@@ -101,8 +102,13 @@ struct pcg_plan {
     uint32_t fss_slab = 0;        // floats of state per codeword
     void* d_trials = nullptr;     // pcg_decode_fsscan_f32_host: trial-count staging (bytes)
     uint64_t trials_frames = 0;
-    bool soft_plan() const { return scan || fsscan; } // SCAN or Fast-SSCAN: no rtc, no 8-bit, no puncturing
-    const char* soft_name() const { return fsscan ? "Fast-SSCAN" : "SCAN"; }
+    // SC-Flip plans (pcg_plan_create_depthfirst; depthfirst.hpp): host.ops holds DepthFirstOp words
+    bool depthfirst = false;
+    uint32_t df_trials = 1;       // trial limit
+    uint32_t df_slab = 0;         // words of state per codeword
+    // SCAN, Fast-SSCAN or SC-Flip: no rtc, no 8-bit, no puncturing
+    bool soft_plan() const { return scan || fsscan || depthfirst; }
+    const char* soft_name() const { return depthfirst ? "SC-Flip" : fsscan ? "Fast-SSCAN" : "SCAN"; }
 };
 
 // The host-pointer pipeline of pcg_decode_f32_host / pcg_decode_i8_host: chunks of the
@@ -747,6 +753,8 @@ static int plan_finish(pcg_plan** out, pcg_plan* p, int device)
         p->wave_cap = pcg::scan_wave_cap(h.N, h.systematic);
     } else if (p->fsscan) {
         p->wave_cap = pcg::fsscan_wave_cap(h.N, p->fss_slab);
+    } else if (p->depthfirst) {
+        p->wave_cap = pcg::depthfirst_wave_cap(h.N, p->df_slab);
     } else if (h.fixed && h.L == 1 && h.sc_kind == 0) {
         p->wave_cap = pcg::sccs_wave_cap(p->wave_lds_floats, false);
         p->wave_cap_i8 = pcg::sccs_wave_cap(p->wave_lds_floats, true);
@@ -893,9 +901,9 @@ int pcg_plan_describe(const pcg_plan* p, pcg_plan_desc* d)
         return fail(PCG_E_ARG, "null argument");
     d->block_length = p->host.N;
     d->info_length = p->host.K;
-    d->list_size = p->scan ? p->scan_iters : p->fsscan ? p->fss_trials : p->host.L;
+    d->list_size = p->scan ? p->scan_iters : p->fsscan ? p->fss_trials : p->depthfirst ? p->df_trials : p->host.L;
     d->node_count = p->host.node_count;
-    d->op_count = (uint32_t)p->host.ops.size() / (p->fsscan ? pcg::FSS_WORDS : 1u);
+    d->op_count = (uint32_t)p->host.ops.size() / (p->fsscan ? pcg::FSS_WORDS : p->depthfirst ? pcg::DF_WORDS : 1u);
     d->lds_bytes = p->wave_lds_floats * 4;
     d->scratch_bytes = p->scratch_floats * 4;
     d->crc_kind = p->host.crc_kind;
@@ -1032,6 +1040,43 @@ static int decode_fsscan(pcg_plan* p, const float* llr, uint64_t F, uint8_t* inf
     return mark_done(p, s);
 }
 
+// DepthFirst::decode (depth_first.cpp:599-638) over F frames: one launch of depthfirst_kernel
+static int decode_depthfirst(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info, uint8_t* ok, uint32_t* bits,
+                             uint8_t* trials, void* stream)
+{
+    const auto& h = p->host;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    pcg::DepthFirstArgs a{};
+    a.llr = llr;
+    a.F = F;
+    a.ops = p->d_ops;
+    a.nops = (uint32_t)h.ops.size() / pcg::DF_WORDS;
+    a.N = h.N;
+    a.K = h.K;
+    a.kb = (h.K + 7) / 8;
+    a.trials = p->df_trials;
+    a.systematic = h.systematic;
+    a.info_pos = p->d_info_pos;
+    a.crc_c0 = h.crc_c0;
+    a.crc_bits = (uint32_t)h.crc_kind;
+    a.crc_rows = p->d_crc_m + h.crc_m.size();
+    a.info = info;
+    a.ok = ok;
+    a.bits = bits;
+    a.ntrials = trials;
+    a.slab_floats = p->df_slab;
+    int rc = order_on(p, s);
+    if (rc != 0)
+        return rc;
+    a.units = (uint32_t)pcg::wave_units(F, 64, p->wave_cap);
+    if ((rc = grow_scratch(p, a.units, sizeof(float), s, 64ull * p->df_slab)) != 0)
+        return rc;
+    a.slab = p->d_scratch;
+    if ((rc = pcg::launch_depthfirst(a, s)) != 0)
+        return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return mark_done(p, s);
+}
+
 static int decode_adaptive(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info, uint8_t* ok, float* metrics,
                            void* stream, const int8_t* llr8 = nullptr)
 {
@@ -1086,6 +1131,8 @@ int pcg_decode_f32(pcg_plan* p,
         return decode_scan(p, llr, F, info, ok, nullptr, nullptr, stream);
     if (p->fsscan)
         return decode_fsscan(p, llr, F, info, ok, nullptr, nullptr, stream);
+    if (p->depthfirst)
+        return decode_depthfirst(p, llr, F, info, ok, nullptr, nullptr, stream);
     if (p->fast)
         return decode_adaptive(p, llr, F, info, ok, metrics, stream);
     return decode_impl(p, llr, F, info, ok, metrics, stream, nullptr, nullptr);
@@ -1618,6 +1665,8 @@ int pcg_decode_f32_host(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info
         return pcg_decode_scan_f32_host(p, llr, F, info, ok, nullptr, nullptr);
     if (p->fsscan)
         return pcg_decode_fsscan_f32_host(p, llr, F, info, ok, nullptr, nullptr);
+    if (p->depthfirst)
+        return pcg_decode_depthfirst_f32_host(p, llr, F, info, ok, nullptr, nullptr);
     DeviceGuard g(p->device);
     return decode_host(p, llr, sizeof(float), F, info, ok, metrics);
 }
@@ -1626,7 +1675,7 @@ static int soft_supported(const pcg_plan* p)
 {
     if (!p)
         return fail(PCG_E_ARG, "null plan");
-    if (p->host.L != 1 || p->host.fixed || p->fast)
+    if (p->host.L != 1 || p->host.fixed || p->fast || p->depthfirst)
         return fail(PCG_E_UNSUPPORTED, "soft codewords: Fast-SSC float plans only (FastSscAvxFloat)");
     if (pcg::sc_soft_lds_bytes(p->host.N) == 0)
         return fail(PCG_E_UNSUPPORTED, "soft codewords: block length too large for one wave's LDS");
@@ -2057,6 +2106,103 @@ int pcg_decode_fsscan_f32_host(pcg_plan* p,
                             "hipMalloc(trial counts)", [&](uint64_t n, void* d_x) {
                                 return decode_fsscan(p, p->d_llr, n, p->d_info, ok ? p->d_ok : nullptr,
                                                      soft ? p->d_soft : nullptr, static_cast<uint8_t*>(d_x), nullptr);
+                            });
+}
+
+int pcg_plan_create_depthfirst(pcg_plan** out,
+                               uint32_t N,
+                               uint32_t trial_limit,
+                               const uint32_t* frozen,
+                               uint32_t n_frozen,
+                               int systematic,
+                               int crc_kind,
+                               int device)
+{
+    if (!out)
+        return fail(PCG_E_ARG, "plan output pointer is null");
+    *out = nullptr;
+    auto* p = new pcg_plan();
+    std::string err;
+    const int rc = pcg::build_depthfirst_plan(p->host, N, trial_limit, frozen, n_frozen, systematic, crc_kind,
+                                              &p->df_slab, &err);
+    if (rc != 0) {
+        delete p;
+        return fail(rc, err);
+    }
+    p->depthfirst = true;
+    p->df_trials = trial_limit;
+    p->host.sc_kind = 0;
+    p->rtc_mode = 0;
+    p->kernel = "depthfirst_kernel";
+    p->wave_lds_floats = pcg::depthfirst_lds_bytes(N) / 4u;
+    p->scratch_floats = p->df_slab; // per codeword
+    return plan_finish(out, p, device);
+}
+
+int pcg_plan_set_depthfirst_trials(pcg_plan* p, uint32_t trial_limit)
+{
+    if (!p)
+        return fail(PCG_E_ARG, "null plan");
+    if (!p->depthfirst)
+        return fail(PCG_E_ARG, "not an SC-Flip plan (pcg_plan_create_depthfirst)");
+    if (trial_limit < 1 || trial_limit > pcg::DF_MAX_TRIALS)
+        return fail(PCG_E_ARG, "SC-Flip: the trial limit must be in [1, 255]");
+    if (p->host.K < std::max<uint32_t>(trial_limit, 2))
+        return fail(PCG_E_ARG, "SC-Flip: needs at least max(trial limit, 2) information bits");
+    p->df_trials = trial_limit;
+    return PCG_OK;
+}
+
+int pcg_decode_depthfirst_f32(pcg_plan* p,
+                              const float* llr,
+                              uint64_t F,
+                              uint8_t* info,
+                              uint8_t* ok,
+                              uint32_t* bits,
+                              uint8_t* trials,
+                              void* stream)
+{
+    if (!p)
+        return fail(PCG_E_ARG, "null plan");
+    if (!p->depthfirst)
+        return fail(PCG_E_ARG, "not an SC-Flip plan (pcg_plan_create_depthfirst)");
+    if (F == 0)
+        return PCG_OK;
+    if (!llr || !info)
+        return fail(PCG_E_ARG, "null llr/info buffer");
+    if (p->device < 0)
+        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
+    if (F > 0xFFFFFFFFull)
+        return fail(PCG_E_ARG, "at most 2^32 - 1 frames per call");
+    DeviceGuard g(p->device);
+    return decode_depthfirst(p, llr, F, info, ok, bits, trials, stream);
+}
+
+int pcg_decode_depthfirst_f32_host(pcg_plan* p,
+                                   const float* llr,
+                                   uint64_t F,
+                                   uint8_t* info,
+                                   uint8_t* ok,
+                                   uint32_t* bits,
+                                   uint8_t* trials)
+{
+    if (!p)
+        return fail(PCG_E_ARG, "null plan");
+    if (!p->depthfirst)
+        return fail(PCG_E_ARG, "not an SC-Flip plan (pcg_plan_create_depthfirst)");
+    if (F == 0)
+        return PCG_OK;
+    if (!llr || !info)
+        return fail(PCG_E_ARG, "null llr/info buffer");
+    if (p->device < 0)
+        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
+    DeviceGuard g(p->device);
+    // the decoded words travel through the chunking helper's soft-codeword staging (N words a frame)
+    return soft_decode_host(p, llr, F, info, ok, reinterpret_cast<float*>(bits), trials, 1, p->d_trials,
+                            p->trials_frames, "hipMalloc(trial counts)", [&](uint64_t n, void* d_x) {
+                                return decode_depthfirst(p, p->d_llr, n, p->d_info, ok ? p->d_ok : nullptr,
+                                                         bits ? reinterpret_cast<uint32_t*>(p->d_soft) : nullptr,
+                                                         static_cast<uint8_t*>(d_x), nullptr);
                             });
 }
 

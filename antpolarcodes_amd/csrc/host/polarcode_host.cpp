@@ -3,6 +3,7 @@
 // top of the C ABI (include/pcg.h).  No device code here.
 #include <polarcode/construction/constructor.h>
 #include <polarcode/decoding/decoder.h>
+#include <polarcode/decoding/depth_first.h>
 #include <polarcode/decoding/fastsscan_float.h>
 #include <polarcode/decoding/scan.h>
 #include <polarcode/encoding/butterfly_fip_packed.h>
@@ -1155,6 +1156,134 @@ void FastSscanFloat::decodeBatchDevice(const float* llr, size_t F, uint8_t* info
                                        void* hipStream)
 {
     decodeBatchSoftDevice(llr, F, info, ok, nullptr, nullptr, hipStream);
+}
+
+// ---- DepthFirst (depth_first.cpp): SC-Flip, successive cancellation with detector-driven bit
+// flips on the GPU ------------------------------------------------------------------------------
+DepthFirst::DepthFirst(size_t blockLength, size_t trialLimit, const std::vector<unsigned>& frozenBits, int device)
+    : mTrialLimit((unsigned)trialLimit), mDevice(device)
+{
+    initialize(blockLength, trialLimit, frozenBits);
+}
+
+DepthFirst::~DepthFirst() { releasePlan(); }
+
+void DepthFirst::releasePlan()
+{
+    if (mPlan)
+        pcg_plan_destroy(mPlan);
+    mPlan = nullptr;
+}
+
+// depth_first.cpp:574-597: float input and output containers, the packed output bytes
+void DepthFirst::initialize(size_t blockLength, size_t trialLimit, const std::vector<unsigned>& frozenBits)
+{
+    Decoder::initialize(blockLength, frozenBits);
+    mTrialLimit = trialLimit > 0xffffffffu ? 0u : (unsigned)trialLimit;
+    mTrials = 0;
+    releasePlan();
+    pcg_plan* probe = nullptr; // validate now, without a GPU
+    const int rc = pcg_plan_create_depthfirst(&probe, (uint32_t)blockLength, mTrialLimit, mFrozenBits.data(),
+                                              (uint32_t)mFrozenBits.size(), 1, 0, -1);
+    if (rc != 0)
+        throw_pcg(rc);
+    pcg_plan_destroy(probe);
+    if (!mExternalContainers) {
+        delete mLlrContainer;
+        delete mBitContainer;
+        delete[] mOutputContainer;
+    }
+    mExternalContainers = false;
+    mLlrContainer = new FloatContainer(mBlockLength, mFrozenBits);
+    mBitContainer = new FloatContainer(mBlockLength, mFrozenBits);
+    mOutputContainer = new unsigned char[(mBlockLength + 7) / 8]();
+}
+
+void DepthFirst::setTrialLimit(size_t trialLimit)
+{
+    const size_t K = mBlockLength - mFrozenBits.size();
+    if (trialLimit < 1 || trialLimit > 255)
+        throw std::logic_error("SC-Flip: the trial limit must be in [1, 255]");
+    if (K < std::max<size_t>(trialLimit, 2))
+        throw std::logic_error("SC-Flip: needs at least max(trial limit, 2) information bits");
+    mTrialLimit = (unsigned)trialLimit;
+}
+
+void DepthFirst::setErrorDetection(ErrorDetection::Detector* pDetector)
+{
+    if (ErrorDetection::gpuKind(pDetector) < 0)
+        throw std::logic_error("detector " + pDetector->getType() + " cannot be evaluated on the GPU");
+    mErrorDetector = pDetector;
+}
+
+void DepthFirst::ensurePlan()
+{
+    const int kind = ErrorDetection::gpuKind(mErrorDetector);
+    if (!(mPlan && kind == mPlanKind && mSystematic == mPlanSystematic)) {
+        releasePlan();
+        const int rc = pcg_plan_create_depthfirst(&mPlan, (uint32_t)mBlockLength, mTrialLimit, mFrozenBits.data(),
+                                                  (uint32_t)mFrozenBits.size(), mSystematic ? 1 : 0, kind, mDevice);
+        if (rc != 0) {
+            mPlan = nullptr;
+            throw_pcg(rc);
+        }
+        mPlanKind = kind;
+        mPlanSystematic = mSystematic;
+    }
+    const int rc = pcg_plan_set_depthfirst_trials(mPlan, mTrialLimit);
+    if (rc != 0)
+        throw_pcg(rc);
+}
+
+bool DepthFirst::decode()
+{
+    ensurePlan();
+    uint8_t ok = 0, trials = 0;
+    const int rc = pcg_decode_depthfirst_f32_host(
+        mPlan, static_cast<FloatContainer*>(mLlrContainer)->data(), 1, mOutputContainer, &ok,
+        reinterpret_cast<uint32_t*>(static_cast<FloatContainer*>(mBitContainer)->data()), &trials);
+    if (rc != 0)
+        throw_pcg(rc);
+    mTrials = trials;
+    return ok != 0;
+}
+
+bool DepthFirst::decodeBatchBits(const float* llr, size_t F, uint8_t* info, uint8_t* ok, uint32_t* bits,
+                                 uint8_t* trials)
+{
+    ensurePlan();
+    std::vector<uint8_t> okv;
+    uint8_t* okp = ok;
+    if (!okp) {
+        okv.assign(F, 0);
+        okp = okv.data();
+    }
+    const int rc = pcg_decode_depthfirst_f32_host(mPlan, llr, F, info, okp, bits, trials);
+    if (rc != 0)
+        throw_pcg(rc);
+    for (size_t f = 0; f < F; ++f)
+        if (!okp[f])
+            return false;
+    return true;
+}
+
+bool DepthFirst::decodeBatch(const float* llr, size_t F, uint8_t* info, uint8_t* ok, float*)
+{
+    return decodeBatchBits(llr, F, info, ok, nullptr, nullptr);
+}
+
+void DepthFirst::decodeBatchBitsDevice(const float* llr, size_t F, uint8_t* info, uint8_t* ok, uint32_t* bits,
+                                       uint8_t* trials, void* hipStream)
+{
+    ensurePlan();
+    const int rc = pcg_decode_depthfirst_f32(mPlan, llr, F, info, ok, bits, trials, hipStream);
+    if (rc != 0)
+        throw_pcg(rc);
+}
+
+void DepthFirst::decodeBatchDevice(const float* llr, size_t F, uint8_t* info, uint8_t* ok, float*, void* hipStream)
+{
+    decodeBatchBitsDevice(llr, F, info, ok, nullptr, nullptr, hipStream);
 }
 
 Decoder* makeDecoder(size_t blockLength, size_t listSize, const std::vector<unsigned>& frozenBits, int impl)

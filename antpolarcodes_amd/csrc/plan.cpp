@@ -2,6 +2,7 @@
 #include "plan.hpp"
 
 #include "crc_host.hpp"
+#include "depthfirst.hpp"
 #include "fsscan.hpp"
 #include "scan.hpp"
 
@@ -441,6 +442,36 @@ void fsscan_emit(PlanHost& p, const std::vector<uint32_t>& f, uint32_t n, uint32
     push(FSS_OUT, fl, er);
 }
 
+// DepthFirst (depth_first.cpp) in decode order: createDecoder's unpruned tree (:524-552; the
+// Repetition / SPC branches are commented out), RateRNode::decode (:277-284) as F, <left>, G,
+// <right>, combine for the nodes above size 8, and one op per size-8 subtree (ShortRateRNode over
+// RateZeroDecoder / RateOneDecoder leaves of block length 1) with its frozen mask and the rank of
+// its first leaf among the information leaves.
+void depthfirst_emit(PlanHost& p, const std::vector<uint8_t>& isf, uint32_t n, uint32_t level, uint32_t group,
+                     uint32_t* rank)
+{
+    if (n == 8) {
+        uint32_t mask = 0;
+        for (uint32_t i = 0; i < 8; ++i)
+            mask |= (uint32_t)isf[group * 8 + i] << i;
+        p.node_count += 15; // 7 ShortRateR nodes over 8 single-bit leaves
+        p.ops.push_back(mkscan(DF_LEAF8, level, group, mask));
+        p.ops.push_back(*rank);
+        *rank += 8u - (uint32_t)__builtin_popcount(mask);
+        return;
+    }
+    p.node_count++;
+    auto push = [&](uint32_t code) {
+        p.ops.push_back(mkscan(code, level, group, 0));
+        p.ops.push_back(0);
+    };
+    push(DF_F);
+    depthfirst_emit(p, isf, n / 2, level + 1, 2 * group, rank);
+    push(DF_G);
+    depthfirst_emit(p, isf, n / 2, level + 1, 2 * group + 1, rank);
+    push(DF_COMB);
+}
+
 int build_impl(PlanHost& p,
                uint32_t N,
                uint32_t L,
@@ -450,11 +481,12 @@ int build_impl(PlanHost& p,
                int crc_kind,
                std::string* err,
                int fixed,
-               int scan, // 1 = SCAN, 2 = Fast-SSCAN
-               uint32_t* slab_floats = nullptr)
+               int scan, // 1 = SCAN, 2 = Fast-SSCAN, 3 = SC-Flip (DepthFirst)
+               uint32_t* slab_floats = nullptr,
+               uint32_t trial_limit = 1)
 {
     p = PlanHost();
-    const std::string who = scan == 2 ? "Fast-SSCAN" : "SCAN";
+    const std::string who = scan == 3 ? "SC-Flip" : scan == 2 ? "Fast-SSCAN" : "SCAN";
     if (scan && (N < 8 || (N & (N - 1)))) {
         *err = who + ": block length must be a power of two >= 8";
         return -1;
@@ -490,6 +522,19 @@ int build_impl(PlanHost& p,
         *err = "CRC INVALID SIZE!"; // errordetector.cpp:33-35
         return -1;
     }
+    if (scan == 3) {
+        // Manager::decode reads hintList[trialLimit - 1] (hintList[1] at limit 1): with fewer
+        // information leaves the reference reads past the vector
+        const uint32_t need = trial_limit > 2 ? trial_limit : 2u;
+        if (trial_limit < 1 || trial_limit > DF_MAX_TRIALS) {
+            *err = "SC-Flip: the trial limit must be in [1, 255]";
+            return -1;
+        }
+        if (N - nf < need) {
+            *err = "SC-Flip: needs at least max(trial limit, 2) information bits";
+            return -1;
+        }
+    }
     p.N = N;
     p.L = L;
     p.log2N = ilog2(N);
@@ -505,7 +550,14 @@ int build_impl(PlanHost& p,
         p.sc_kind = (k && std::string(k) == "wave") ? 1 : ((k && std::string(k) == "scs") ? 0 : 2);
     }
     try {
-        if (scan == 2) {
+        if (scan == 3) {
+            std::vector<uint8_t> isf(N, 0);
+            for (uint32_t v : p.frozen)
+                isf[v] = 1;
+            uint32_t rank = 0;
+            depthfirst_emit(p, isf, N, 0, 0, &rank);
+            *slab_floats = df_slab_floats(N, p.K);
+        } else if (scan == 2) {
             uint32_t top = fsscan_er(N);
             fsscan_emit(p, p.frozen, N, 0, 0, fsscan_el(N), &top);
             *slab_floats = top;
@@ -626,6 +678,19 @@ int build_fsscan_plan(PlanHost& p,
                       std::string* err)
 {
     return build_impl(p, N, 1, frozen, nf, systematic, crc_kind, err, 0, 2, slab_floats);
+}
+
+int build_depthfirst_plan(PlanHost& p,
+                          uint32_t N,
+                          uint32_t trial_limit,
+                          const uint32_t* frozen,
+                          uint32_t nf,
+                          int systematic,
+                          int crc_kind,
+                          uint32_t* slab_floats,
+                          std::string* err)
+{
+    return build_impl(p, N, 1, frozen, nf, systematic, crc_kind, err, 0, 3, slab_floats, trial_limit);
 }
 
 } // namespace pcg

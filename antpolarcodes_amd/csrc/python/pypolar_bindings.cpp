@@ -9,6 +9,7 @@
 
 #include <polarcode/construction/constructor.h>
 #include <polarcode/decoding/decoder.h>
+#include <polarcode/decoding/depth_first.h>
 #include <polarcode/decoding/fastsscan_float.h>
 #include <polarcode/decoding/scan.h>
 #include <polarcode/encoding/butterfly_fip_packed.h>
@@ -38,6 +39,11 @@ struct PyScan {
 
 struct PyFastSscan {
     std::unique_ptr<Decoding::FastSscanFloat> dec;
+    std::unique_ptr<ErrorDetection::Detector> det;
+};
+
+struct PyDepthFirst {
+    std::unique_ptr<Decoding::DepthFirst> dec;
     std::unique_ptr<ErrorDetection::Detector> det;
 };
 
@@ -434,6 +440,94 @@ PYBIND11_MODULE(_pypolar, m)
             },
             py::arg("llr_ptr"), py::arg("frames"), py::arg("info_ptr"), py::arg("ok_ptr") = 0,
             py::arg("soft_ptr") = 0, py::arg("trials_ptr") = 0, py::arg("stream") = 0);
+
+    // the reference's Decoding::DepthFirst (depth_first.h) with PolarDecoder's accessors
+    py::class_<PyDepthFirst>(m, "DepthFirstDecoder")
+        .def(py::init([](size_t N, size_t trials, std::vector<unsigned> frozen) {
+                 auto d = std::make_unique<PyDepthFirst>();
+                 d->dec = std::make_unique<Decoding::DepthFirst>(N, trials, frozen);
+                 d->det = std::make_unique<ErrorDetection::CRC8>(); // as makeDecoder would install
+                 d->dec->setErrorDetection(d->det.get());
+                 return d;
+             }),
+             py::arg("blockLength"), py::arg("trialLimit"), py::arg("frozenBitPositions"))
+        .def("blockLength", [](PyDepthFirst& s) { return s.dec->blockLength(); })
+        .def("infoLength", [](PyDepthFirst& s) { return s.dec->infoLength(); })
+        .def("listSize", [](PyDepthFirst& s) { return s.dec->getListSize(); })
+        .def("trials", [](PyDepthFirst& s) { return s.dec->trials(); })
+        .def("setTrialLimit", [](PyDepthFirst& s, size_t v) { s.dec->setTrialLimit(v); })
+        .def("setSystematic", [](PyDepthFirst& s, bool v) { s.dec->setSystematic(v); })
+        .def("isSystematic", [](PyDepthFirst& s) { return s.dec->isSystematic(); })
+        .def("frozenBits", [](PyDepthFirst& s) { return s.dec->frozenBits(); })
+        .def("getErrorDetectionMode", [](PyDepthFirst& s) { return s.dec->getErrorDetectionMode(); })
+        .def(
+            "setErrorDetection",
+            [](PyDepthFirst& s, unsigned size, std::string type) {
+                std::unique_ptr<ErrorDetection::Detector> d(ErrorDetection::create(size, type));
+                s.dec->setErrorDetection(d.get());
+                s.det = std::move(d);
+            },
+            py::arg("size") = 0, py::arg("type") = "crc")
+        .def("decode_vector",
+             [](PyDepthFirst& s, const f32array& a) {
+                 py::buffer_info in = a.request();
+                 if (in.ndim != 1)
+                     throw std::runtime_error("Only ONE-dimensional vectors allowed!");
+                 if ((size_t)in.size != s.dec->blockLength())
+                     throw std::runtime_error("Input vector size != blockSize // 8!");
+                 auto res = py::array_t<uint8_t>(s.dec->infoLength() / 8);
+                 std::vector<uint8_t> tmp(s.dec->infoLength() / 8 + 8);
+                 s.dec->decode_vector(static_cast<const float*>(in.ptr), tmp.data());
+                 std::memcpy(res.request().ptr, tmp.data(), s.dec->infoLength() / 8);
+                 return res;
+             })
+        .def("getSoftCodeword",
+             [](PyDepthFirst& s) {
+                 py::array_t<float> out(s.dec->blockLength());
+                 s.dec->getSoftCodeword(out.mutable_data());
+                 return out;
+             })
+        .def(
+            "decode_batch",
+            [](PyDepthFirst& s, const f32array& a, bool return_ok, bool return_bits, bool return_trials) -> py::object {
+                py::buffer_info in = a.request();
+                const size_t N = s.dec->blockLength();
+                if (in.ndim != 2 || (size_t)in.shape[1] != N)
+                    throw std::runtime_error("decode_batch expects a (frames, blockLength) float32 array");
+                const size_t F = (size_t)in.shape[0], kb = (s.dec->infoLength() + 7) / 8;
+                py::array_t<uint8_t> info({ F, kb });
+                py::array_t<uint8_t> ok(F), trials(return_trials ? F : 0);
+                py::array_t<uint32_t> bits({ return_bits ? F : 0, N });
+                {
+                    py::gil_scoped_release nogil;
+                    s.dec->decodeBatchBits(static_cast<const float*>(in.ptr), F, info.mutable_data(), ok.mutable_data(),
+                                           return_bits ? bits.mutable_data() : nullptr,
+                                           return_trials ? trials.mutable_data() : nullptr);
+                }
+                if (!return_ok && !return_bits && !return_trials)
+                    return std::move(info);
+                py::list t;
+                t.append(info);
+                if (return_ok)
+                    t.append(ok);
+                if (return_bits)
+                    t.append(bits);
+                if (return_trials)
+                    t.append(trials);
+                return py::tuple(t);
+            },
+            py::arg("llrs"), py::arg("return_ok") = false, py::arg("return_bits") = false,
+            py::arg("return_trials") = false)
+        .def(
+            "decode_device",
+            [](PyDepthFirst& s, uintptr_t llr, size_t F, uintptr_t info, uintptr_t ok, uintptr_t bits, uintptr_t trials,
+               uintptr_t stream) {
+                s.dec->decodeBatchBitsDevice(reinterpret_cast<const float*>(llr), F, reinterpret_cast<uint8_t*>(info),
+                                             reinterpret_cast<uint8_t*>(ok), reinterpret_cast<uint32_t*>(bits),
+                                             reinterpret_cast<uint8_t*>(trials), reinterpret_cast<void*>(stream));
+            },
+            py::arg("llr_ptr"), py::arg("frames"), py::arg("info_ptr"), py::arg("ok_ptr") = 0,
+            py::arg("bits_ptr") = 0, py::arg("trials_ptr") = 0, py::arg("stream") = 0);
 
     py::class_<PyEncoder>(m, "PolarEncoder")
         .def(py::init([](size_t N, std::vector<unsigned> frozen) {

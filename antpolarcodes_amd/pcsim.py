@@ -4,12 +4,13 @@ Restates `Simulation::Simulator` / `SimulationWorker` (src/simulation/simulator.
 david13pod/antPolarCodes) around the batched GPU decoders:
 
   * job list: configureSingleRun / CodeLength / DesignSnr / ListLength / Rate /
-    Amplification / ScanSim (simulator.cpp:126-340), then snrInflateJobList (:361-379), with the
+    Amplification / DepthFirstSim / ScanSim (simulator.cpp:126-340), then snrInflateJobList (:361-379), with the
     reference's float32 arithmetic for the SNR / design-SNR / rate / amplification grids;
   * per job (SimulationWorker::run, :632-672): Bhattacharyya frozen set (:680-697),
     encoder + decoder by precision and list size (setCoders :699-760: L > 1 -> Adaptive
     {Char, Float, Mixed}, L == 1 -> FastSscFipChar / FastSscAvxFloat; simtypes scan and
-    fastsscan -> Scan / FastSscanFloat with L as iteration / trial limit, -p 32 only), CRC-8 / CRC-32 /
+    fastsscan -> Scan / FastSscanFloat with L as iteration / trial limit, simtype depthfirst ->
+    DepthFirst with L as trial limit, all three -p 32 only), CRC-8 / CRC-32 /
     none (setErrorDetector :761-805; "cmac*" is outside this build), BPSK-AWGN at
     Es/N0 = Eb/N0 * BPS * K / N (setChannel :806-824), Scale(amplification) of the
     demodulated symbols (:920-937), warm-up min(blocks / 8, 1000) blocks, then the
@@ -40,8 +41,8 @@ import numpy as np
 
 SIMTYPES = ("single", "codelength", "designsnr", "listlength", "rate", "amplification", "fixed", "depthfirst",
             "scan", "fastsscan", "ask", "compareall", "getcode")
-SUPPORTED = ("single", "codelength", "designsnr", "listlength", "rate", "amplification", "scan", "fastsscan",
-             "getcode")
+SUPPORTED = ("single", "codelength", "designsnr", "listlength", "rate", "amplification", "depthfirst", "scan",
+             "fastsscan", "getcode")
 CSV_HEADER = ('"N","K","dSNR","C","L","Eb/N0","BPS","BLER","BER","RER","Runs","Errors","Time","Blockspeed",'
               '"Coded Bitrate","Payload Bitrate","Effective Payload Bitrate","Encoder Bitrate","Amplification",'
               '"time min","time max","time mean","time deviation"')
@@ -78,7 +79,9 @@ class Job:
     amplification: float
     bitsPerSymbol: int = 1
     name: str = ""
-    decoder: str = ""  # decoderType: "" = tFlexible (by precision and L), "scan" = tScan, "fastsscan" = tFastSscan
+    # decoderType: "" = tFlexible (by precision and L), "scan" = tScan, "fastsscan" = tFastSscan,
+    # "depthfirst" = tDepthFirst
+    decoder: str = ""
     runs: int = 0
     bits: int = 0
     errors: int = 0
@@ -146,8 +149,9 @@ def configure(a):
         return jobs
     if st == "amplification":
         return [replace(t, amplification=v) for v in _grid(a.amp_min, a.amp_max, int(a.amp_count))]
-    if st in ("scan", "fastsscan"):
-        # configureScanSim (:323-340): L is the iteration (scan) or trial (fastsscan) limit.  Both
+    if st in ("scan", "fastsscan", "depthfirst"):
+        # configureScanSim (:323-340) and configureDepthFirstSim (:303-321): L is the iteration
+        # (scan) or trial (fastsscan, depthfirst) limit.  All three
         # decoders are float decoders (setCoders :717-720 ignores the precision); this build asks
         # for it explicitly.  (With the default precision, 832, this is where `pcsim scan` exits:
         # test_pcsim.py's SystemExit assertion for "scan", written when the type itself was
@@ -260,7 +264,7 @@ class GpuBackend:
 
     def setup(self, job):
         from .construction import frozen_bits
-        from ._native import Encoder, FastSscanPlan, Plan, ScanPlan
+        from ._native import DepthFirstPlan, Encoder, FastSscanPlan, Plan, ScanPlan
         if job.errorDetection >= job.K:  # setErrorDetector (:763-766)
             job.errorDetection, job.errorDetectionType = 0, "none"
         if job.errorDetectionType == "cmac":
@@ -270,10 +274,11 @@ class GpuBackend:
         self.frozen = frozen_bits(job.N, job.K, job.designSNR, "BB")
         self.enc = Encoder(job.N, self.frozen, systematic=job.systematic, crc=crc, device=self.device)
         self.second = None
-        if job.decoder in ("scan", "fastsscan"):  # new Scan / FastSscanFloat(N, L, frozen) (:717-720)
+        # new DepthFirst / Scan / FastSscanFloat(N, L, frozen) (:715-720)
+        if job.decoder in ("scan", "fastsscan", "depthfirst"):
             if job.precision != 32:
                 raise SystemExit(f"No {job.decoder} decoder present for {job.precision}-bit decoding (use -p 32).")
-            make = ScanPlan if job.decoder == "scan" else FastSscanPlan
+            make = {"scan": ScanPlan, "fastsscan": FastSscanPlan, "depthfirst": DepthFirstPlan}[job.decoder]
             self.plan = make(job.N, job.L, self.frozen, job.systematic, crc, self.device)
         elif job.L > 1 and job.precision == 832:  # AdaptiveMixed: FastSscFipChar, then SclAvxFloat
             self.plan = Plan(job.N, 1, self.frozen, job.systematic, crc, self.device, fixed=True)

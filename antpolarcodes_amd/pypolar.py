@@ -16,13 +16,18 @@ decoder type string "scan" of PolarDecoder is not routed to it yet.
 FastSscanDecoder(blockLength, trialLimit, frozenBitPositions) is the reference's Fast-SSCAN decoder
 (Decoding::FastSscanFloat): the same soft output from closed-form subtrees, passes repeated only
 while the detector check fails (decodeAgain() adds one; decode_batch(..., return_trials=True)
-reports the passes run).  The native module is mandatory: there is no CPU fallback.
+reports the passes run).
+DepthFirstDecoder(blockLength, trialLimit, frozenBitPositions) is the reference's SC-Flip decoder
+(Decoding::DepthFirst): plain successive cancellation, decoded again with the least reliable
+information-bit decisions flipped while the detector check fails (decode_batch(...,
+return_bits=True, return_trials=True) returns the decoded words and the trials run).  The native module is mandatory: there is no CPU fallback.
 """
 from ._native import _prefer_torch_hip_runtime
 
 _prefer_torch_hip_runtime()  # share PyTorch's HIP runtime (see _native.py)
 
-from ._pypolar import (Detector, FastSscanDecoder, PolarDecoder, PolarEncoder, Puncturer, ScanDecoder,  # noqa: E402
+from ._pypolar import (DepthFirstDecoder, Detector, FastSscanDecoder, PolarDecoder, PolarEncoder, Puncturer, ScanDecoder,  # noqa: E402
                        frozen_bits)
 
-__all__ = ["PolarDecoder", "PolarEncoder", "Detector", "Puncturer", "ScanDecoder", "FastSscanDecoder", "frozen_bits"]
+__all__ = ["PolarDecoder", "PolarEncoder", "Detector", "Puncturer", "ScanDecoder", "FastSscanDecoder",
+           "DepthFirstDecoder", "frozen_bits"]

@@ -1,11 +1,12 @@
-"""Time the SCAN or the Fast-SSCAN kernel on device-resident frames:
-python -m antpolarcodes_amd.scan_time [--decoder {scan,fastsscan}]
+"""Time the SCAN, the Fast-SSCAN or the SC-Flip kernel on device-resident frames:
+python -m antpolarcodes_amd.scan_time [--decoder {scan,fastsscan,depthfirst}]
 
 HIP events around ScanPlan.decode_device (or FastSscanPlan.decode_device) on AWGN frames already
 on the GPU (N = 1024, K = 512, CRC-8, 2^14 frames by default), 3 warm-ups, the median of 20 runs,
-at 1 and 4 iterations (fastsscan: trial limits), with info and ok only and again with the soft
-codeword.  Prints one JSON line per configuration; for fastsscan it also carries the mean number
-of passes run per frame.
+at 1 and 4 iterations (fastsscan: trial limits; depthfirst: trial limits 1 and 8), with info and ok
+only and again with the soft codeword (depthfirst: the decoded words).  Prints one JSON line per
+configuration; for fastsscan and depthfirst it also carries the mean number of passes (trials) run
+per frame.
 """
 import argparse
 import json
@@ -19,17 +20,19 @@ def main():
     ap.add_argument("--n", type=int, default=1024)
     ap.add_argument("--k", type=int, default=512)
     ap.add_argument("--frames", type=int, default=1 << 14)
-    ap.add_argument("--iterations", type=int, nargs="+", default=[1, 4])
+    ap.add_argument("--iterations", type=int, nargs="+", default=None)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--ebn0", type=float, default=2.0)
-    ap.add_argument("--decoder", choices=("scan", "fastsscan"), default="scan")
+    ap.add_argument("--decoder", choices=("scan", "fastsscan", "depthfirst"), default="scan")
     a = ap.parse_args()
+    if a.iterations is None:
+        a.iterations = [1, 8] if a.decoder == "depthfirst" else [1, 4]
 
     import torch
 
     from . import frames
-    from ._native import FastSscanPlan, ScanPlan
+    from ._native import DepthFirstPlan, FastSscanPlan, ScanPlan
     from .construction import frozen_bits
 
     fr = frozen_bits(a.n, a.k, 0.0)
@@ -38,11 +41,14 @@ def main():
     dev = torch.device("cuda:0")
     x = torch.from_numpy(np.ascontiguousarray(llr)).to(dev).repeat((a.frames + base - 1) // base, 1)[:a.frames]
     x = x.contiguous()
-    fast = a.decoder == "fastsscan"
-    plan = (FastSscanPlan if fast else ScanPlan)(a.n, 1, fr, crc=8)
+    fast = a.decoder != "scan"  # detector-terminated: a trial limit, and the trials run come back
+    plan = {"scan": ScanPlan, "fastsscan": FastSscanPlan, "depthfirst": DepthFirstPlan}[a.decoder](a.n, 1, fr,
+                                                                                                   crc=8)
     info = torch.empty((a.frames, plan.kb), dtype=torch.uint8, device=dev)
     ok = torch.empty((a.frames,), dtype=torch.uint8, device=dev)
-    soft = torch.empty((a.frames, a.n), dtype=torch.float32, device=dev)
+    # the soft codeword; depthfirst: the decoded words
+    soft = torch.empty((a.frames, a.n), dtype=torch.int32 if a.decoder == "depthfirst" else torch.float32,
+                       device=dev)
     trials = torch.empty((a.frames,), dtype=torch.uint8, device=dev) if fast else None
     d = plan.describe()
     for it in a.iterations:

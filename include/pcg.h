@@ -40,6 +40,11 @@
  *   pcg_plan_set_fsscan_trials <- the trial limit; forced passes serve decodeAgain :320-325
  *   pcg_decode_fsscan_f32[_host] <- FastSscanFloat::decode :309-339 (RateRNode::decode :116-163,
  *                        RepetitionNode :202-223, TwoBitNode :231-235), batched
+ *   pcg_plan_create_depthfirst <- new Decoding::DepthFirst(N, trialLimit, frozen)
+ *                        (src/polarcode/decoding/depth_first.cpp:556-597, createDecoder :524-552)
+ *   pcg_plan_set_depthfirst_trials <- the trial limit of later decodes
+ *   pcg_decode_depthfirst_f32[_host] <- DepthFirst::decode :599-638 (Manager::decode :28-82,
+ *                        decodeNext :85-153, RateRNode::decode :277-284), batched
  *   pcg_plan_destroy  <- Decoder::~Decoder decoder.cpp:104-114
  *   pcg_last_error    <- the std::exception text the reference throws
  *   pcg_puncturer_*   <- PolarCode::Puncturer (include/polarcode/puncturer.h:33-99,
@@ -354,6 +359,61 @@ int pcg_decode_fsscan_f32_host(pcg_plan* plan,
                                uint8_t* ok,
                                float* soft,
                                uint8_t* trials);
+
+/* ---- SC-Flip: successive cancellation with detector-driven bit flips ----------------------
+ * (Decoding::DepthFirst, depth_first.cpp.)  A frame is decoded with plain successive cancellation
+ * down to single bits; while its detector check fails, the reference's search configures the
+ * least reliable information-bit decisions (|LLR| at the leaf) to be flipped and the frame is
+ * decoded again, up to trial_limit full decodes (1 .. 255).  When the trials run out the output
+ * is the LAST trial's decode, as in the reference.  Outputs equal the reference's bit for bit:
+ * the info bytes (sign bits at the information positions; a non-systematic plan re-encodes
+ * first), ok, and `bits`, the F x N 32-bit words of the decoded codeword that getSoftCodeword
+ * returns (an information leaf's LLR, negated where flipped, +inf at a frozen leaf, XOR-combined
+ * upwards: only the sign bits are decisions); `trials` is the number of decodes each frame ran.
+ * With the dummy detector (crc_kind 0) every frame stops after trial 1.  One deviation: leaves
+ * of EQUAL reliability are ordered by leaf index here (a stable sort), where the reference's
+ * order is whatever std::sort leaves; frames whose search meets no tie are
+ * identical.  Contract: finite LLRs whose sums stay finite.  N: a power of two, 8 <= N <= 4096
+ * (PCG_E_UNSUPPORTED above); any strictly ascending frozen set with K >= max(trial_limit, 2)
+ * information bits (PCG_E_ARG below: the reference reads past its reliability list).
+ * pcg_plan_describe reports list_size = trial_limit, lds_bytes of a wave and scratch_bytes per
+ * codeword; pcg_plan_kernel_name is "depthfirst_kernel".  pcg_decode_f32[_host] work;
+ * pcg_plan_specialize[_async], pcg_decode_f32_soft[_host], pcg_decode_i8[_host] and
+ * pcg_decode_punctured_f32 return PCG_E_UNSUPPORTED, the SCAN and Fast-SSCAN entry points
+ * PCG_E_ARG. */
+int pcg_plan_create_depthfirst(pcg_plan** plan,
+                               uint32_t N,
+                               uint32_t trial_limit,
+                               const uint32_t* frozen,
+                               uint32_t n_frozen,
+                               int systematic,
+                               int crc_kind,
+                               int device);
+
+/* The trial limit (1 .. 255, at most K) of later decodes. */
+int pcg_plan_set_depthfirst_trials(pcg_plan* plan, uint32_t trial_limit);
+
+/* Decode F frames with an SC-Flip plan (PCG_E_ARG for any other plan).  Device pointers,
+ * asynchronous, stream-ordered like pcg_decode_f32.  info: F x ceil(K/8) bytes.  ok (F bytes),
+ * bits (F x N words, natural order) and trials (F bytes) may be NULL: an output not asked for
+ * costs no stores. */
+int pcg_decode_depthfirst_f32(pcg_plan* plan,
+                              const float* llr,
+                              uint64_t F,
+                              uint8_t* info,
+                              uint8_t* ok,
+                              uint32_t* bits,
+                              uint8_t* trials,
+                              void* stream);
+
+/* Same with HOST pointers; synchronous.  Streams the batch through device buffers in chunks. */
+int pcg_decode_depthfirst_f32_host(pcg_plan* plan,
+                                   const float* llr,
+                                   uint64_t F,
+                                   uint8_t* info,
+                                   uint8_t* ok,
+                                   uint32_t* bits,
+                                   uint8_t* trials);
 
 int pcg_plan_describe(const pcg_plan* plan, pcg_plan_desc* desc);
 
