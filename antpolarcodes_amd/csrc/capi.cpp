@@ -242,8 +242,9 @@ void free_plan_device(pcg_plan* p)
 constexpr uint64_t RTC_AUTO_FRAMES = 8192;
 
 // Plans with a specialised kernel: Fast-SSC float plans on the LDS-resident kernel (the walk
-// unrolled), float list plans (their layout and plan constants as literals, the schedule
-// loop kept: a fully unrolled walk -- 280 schedule words for config 3, each op inlining path
+// unrolled), float list plans (their layout and plan constants as literals and, for list
+// widths up to 8, the walk compiled per op class, scl_rtc_source; wider ones keep the schedule
+// loop: a fully unrolled walk -- 280 schedule words for config 3, each op inlining path
 // selection and the leaf decoders -- had not compiled after 20 minutes, against 34 s for
 // config 2's 60 fused Fast-SSC ops; PCG_RTC_SCL=0 keeps list plans on the interpreter), the
 // 8-bit lane-serial kernels, and both stages of adaptive plans; never with the op profiler.
@@ -553,6 +554,34 @@ int pcg_dev_plan_ops(const pcg_plan* p, uint32_t* out, int n)
     return (int)ops.size();
 }
 
+// Development aid, not part of include/pcg.h: the op classes the specialised list kernel's walk
+// is compiled for (sclls_kernel.hip ls_classify, run here on the plan's schedule and layout as the
+// kernel source runs it at compile time).  keys[0 .. *ncls): code | stage << 8 | fused << 16;
+// pos: two words per walk position (class id | words consumed << 8 | offset << 16, then the
+// second schedule word consumed or 0).  Returns the number of positions (pos holds the first
+// npos of them); PCG_E_UNSUPPORTED for a plan that is not a float list plan.
+int pcg_dev_rtc_classes(const pcg_plan* p, uint32_t* keys, int nkeys, uint32_t* pos, int npos, int* ncls)
+{
+    if (!p || !keys || !pos || !ncls || nkeys < 0 || npos < 0)
+        return fail(PCG_E_ARG, "null argument");
+    if (p->host.fixed || p->host.L < 2 || p->soft_plan())
+        return fail(PCG_E_UNSUPPORTED, "op classes: not a float list plan");
+    const auto& ops = p->host.ops;
+    std::vector<uint32_t> k, q(2 * ops.size() + 2);
+    const int n = pcg::sclls_rtc_classes(ops.data(), (uint32_t)ops.size(), p->host.log2N, p->lds_stage_limit,
+                                         p->scl_virt, p->scl_fuse, &k, q.data());
+    if (n < 0)
+        return fail(PCG_E_UNSUPPORTED, "op classes: too many classes");
+    for (int i = 0; i < nkeys && i < (int)k.size(); ++i)
+        keys[i] = k[i];
+    for (int i = 0; i < npos && i < n; ++i) {
+        pos[2 * i] = q[2 * i];
+        pos[2 * i + 1] = q[2 * i + 1];
+    }
+    *ncls = (int)k.size();
+    return n;
+}
+
 // Development aid, not part of include/pcg.h: hiprtc compiles this process started.
 int pcg_dev_rtc_compiles(void) { return pcg::rtc_compiles(); }
 
@@ -685,6 +714,8 @@ static int plan_create_impl(pcg_plan** out,
             p->dev_overrides |= PCG_DEV_BUILD;
     }
     if (getenv("PCG_RTC_XOPTS")) // extra compiler options for the specialised kernels
+        p->dev_overrides |= PCG_DEV_BUILD;
+    if (!fixed && L > 1 && getenv("PCG_RTC_CLASSES")) // the specialised list walk's A/B switch (scl_rtc_source)
         p->dev_overrides |= PCG_DEV_BUILD;
     if (const char* e = getenv("PCG_RTC_SCL"); e && e[0] == '0') {
         p->rtc_scl = false;

@@ -495,6 +495,13 @@ std::string scl_rtc_source(const PlanHost& h, uint32_t lp, uint32_t Sl, uint32_t
     def("V3", v3);
     def("SB", sb);
     def("FUSE", fuse);
+    // the walk compiled per op class (sclls_kernel.hip, PCG_RTC_CLASSES): list widths up to 8;
+    // wider ones (config 5: 256 VGPRs with spills already) keep the schedule loop.
+    // PCG_RTC_CLASSES=0/1 in the environment: dev override for A/B runs of one tree
+    uint32_t classes = lp <= 8 ? 1u : 0u;
+    if (const char* e = getenv("PCG_RTC_CLASSES"))
+        classes = e[0] == '0' ? 0u : 1u;
+    def("CLASSES", classes);
     s += "#define PCG_RTC_OPS";
     for (size_t k = 0; k < h.ops.size(); ++k)
         s += (k ? "," : " ") + std::to_string(h.ops[k]) + "u";

@@ -25,6 +25,13 @@ std::string sclc_rtc_source(const PlanHost& h, uint32_t lp, uint32_t Sl);
 // sclls_kernel.hip (host part): "#define PCG_LS_... <value>" lines of that translation unit's
 // compile-time knobs; *nondefault = a knob differs from the source's default (a dev build)
 std::string sclls_rtc_defines(bool* nondefault);
+// sclls_kernel.hip (host part): the op classes of a list schedule, derived by the function the
+// specialised kernel evaluates at compile time (ls_classify).  keys: code | stage << 8 | fused
+// << 16 per class; pos (2 * nops words at least): per walk position class id | words consumed
+// << 8 | offset << 16, then the second word consumed or 0.  Returns the positions, -1: too
+// many classes.
+int sclls_rtc_classes(const uint32_t* ops, uint32_t nops, uint32_t log2N, uint32_t Sl, uint32_t virt, uint32_t fuse,
+                      std::vector<uint32_t>* keys, uint32_t* pos);
 
 // One compile of one generated source, shared by every plan (and thread) asking for it.
 struct RtcJob;

@@ -2882,15 +2882,160 @@ PCG_DEV void ls_op(Ls<LP>& c, uint32_t code, uint32_t s, uint32_t o, uint32_t& P
     wsync();
 }
 
+// ---- op classes of a schedule (the plan-specialised walk) -------------------------------
+// A class is what the walk's helpers branch on per op: (op code, stage, fused with the child's
+// F), packed as code | stage << 8 | fused << 16.  A schedule of a few hundred words has a few
+// dozen of them (config 3: 280 words, 35 classes).  ls_classify walks the schedule exactly as
+// the interpreter loop of sclls_body does (the same fusion rule, the same words consumed) and
+// emits, per walk position, two words: class id | words consumed << 8 | offset << 16, then the
+// second schedule word the position consumes (an ST8's descriptor, a fused op's child F) or 0.
+// Returns the number of positions, or ~0u when the schedule has more than LS_MAXCLS classes.
+constexpr uint32_t LS_MAXCLS = 128;
+constexpr PCG_HD inline uint32_t ls_class_code(uint32_t key) { return key & 0xffu; }
+constexpr PCG_HD inline uint32_t ls_class_stage(uint32_t key) { return (key >> 8) & 0xffu; }
+constexpr PCG_HD inline bool ls_class_fused(uint32_t key) { return ((key >> 16) & 1u) != 0; }
+constexpr PCG_HD inline uint32_t ls_classify(const uint32_t* ops, uint32_t nops, uint32_t Sl, uint32_t mt,
+                                             uint32_t fusebits, uint32_t* keys, uint32_t* ncls, uint32_t* pos)
+{
+    uint32_t nc = 0, np = 0;
+    for (uint32_t k = 0; k < nops; ++k) {
+        const uint32_t w = ops[k];
+        const uint32_t code = op_code(w), s = op_stage(w);
+        bool fuse = false;
+        if ((code == OP_F || code == OP_G) && s >= 5 && s - 1 >= Sl && s - 1 < mt && (fusebits & 1u) && k + 1 < nops)
+            fuse = op_code(ops[k + 1]) == OP_F && op_stage(ops[k + 1]) == s - 1;
+        const bool two = fuse || (code == OP_S_ST8 && k + 1 < nops);
+        const uint32_t key = code | s << 8 | (fuse ? 1u << 16 : 0u);
+        uint32_t id = 0;
+        while (id < nc && keys[id] != key)
+            ++id;
+        if (id == nc) {
+            if (nc == LS_MAXCLS)
+                return ~0u;
+            keys[nc++] = key;
+        }
+        pos[2 * np] = id | (two ? 2u : 1u) << 8 | op_off(w) << 16;
+        pos[2 * np + 1] = two ? ops[k + 1] : 0u;
+        ++np;
+        if (two)
+            ++k;
+    }
+    *ncls = nc;
+    return np;
+}
+
 #ifdef PCG_RTC
-// Plan-specialised walk (rtc.cpp): the plan's schedule as literals (PCG_RTC_OPS), unrolled
-// at compile time with every op's code, stage, offset, fusion and descriptor constant
-// (PCG_RTC_UNROLL = 1; measured: config 3's kernel did not compile within 20 minutes).  By
-// default the specialised list kernel keeps the schedule loop and only its layout and plan
-// constants are literals (scl_rtc_kernel).
+// Plan-specialised walk (rtc.cpp): the plan's schedule as literals (PCG_RTC_OPS).
+//   * PCG_RTC_CLASSES (default for LP <= 8): one inlined copy of ls_op per op class, its code,
+//     stage and fusion literals, so every trip count, storage choice (with_stage) and slot-table
+//     shift of the helpers folds; the walk is a loop over positions that reads (class id,
+//     offset, descriptor) through the scalar cache and branches on the class id.
+//   * PCG_RTC_UNROLL = 1: every position inlined with its offset and descriptor constant too
+//     (measured: config 3's kernel did not compile within 20 minutes).
+//   * neither: the interpreter's schedule loop with only the layout and plan constants
+//     literal.
 constexpr uint32_t rtc_ops[] = { PCG_RTC_OPS };
 constexpr uint32_t rtc_nops = sizeof(rtc_ops) / sizeof(rtc_ops[0]);
 constexpr uint32_t rtc_mt = ls_mtop(PCG_RTC_LOG2N, PCG_RTC_VIRT);
+
+#ifndef PCG_RTC_CLASSES
+#define PCG_RTC_CLASSES 0
+#endif
+#if PCG_RTC_CLASSES && !PCG_RTC_UNROLL && !defined(PCG_LS_PROF)
+#define PCG_LS_CLASSES 1
+struct RtcTab {
+    uint32_t ncls, npos;
+    uint32_t keys[LS_MAXCLS];
+    uint32_t pos[2 * rtc_nops];
+};
+constexpr RtcTab rtc_make_tab()
+{
+    RtcTab t{};
+    t.npos = ls_classify(rtc_ops, rtc_nops, PCG_RTC_SL, rtc_mt, PCG_RTC_FUSE, t.keys, &t.ncls, t.pos);
+    return t;
+}
+constexpr RtcTab rtc_tab = rtc_make_tab();
+static_assert(rtc_tab.npos != ~0u && rtc_tab.ncls >= 1u, "more op classes than LS_MAXCLS (or none)");
+// the per-position table the walk reads (constant address space: scalar loads)
+__constant__ const RtcTab rtc_dtab = rtc_make_tab();
+
+// with_stage for a literal stage: the same choice, made at instantiation from the kernel's
+// literals (c.vlow = PCG_RTC_V3, c.Sl = PCG_RTC_SL, c.mt = rtc_mt, c.top = PCG_RTC_LOG2N), so a
+// class instantiates its leaf decoder for the one storage it reads, not for all nine
+template <uint32_t S, int LP, typename Fn>
+PCG_DEV void with_stage_lit(const Ls<LP>& c, uint32_t o, Fn&& fn)
+{
+    constexpr uint32_t Sl = PCG_RTC_SL, vlow = PCG_RTC_V3, top = PCG_RTC_LOG2N;
+    if constexpr (vlow >= 2u && S <= 4u) { // stage 4 recomputed from stage 5 (and stage 3 from it)
+        auto go = [&](auto s5) {
+            const V4St<LP, decltype(s5)> v4{ &c, s5, o & ~15u };
+            if constexpr (S == 4u)
+                fn(v4);
+            else
+                fn(V3St<LP, decltype(v4)>{ &c, v4, o });
+        };
+        if constexpr (5u < Sl)
+            go(lds_st(c, 5));
+        else
+            go(gl_st(c, 5));
+    } else if constexpr (vlow >= 1u && S == 3u) {
+        if constexpr (4u < Sl)
+            fn(V3St<LP, LdsSt>{ &c, lds_st(c, 4), o });
+        else
+            fn(V3St<LP, GlSt>{ &c, gl_st(c, 4), o });
+    } else if constexpr (S >= rtc_mt) {
+        fn(VirtSt<LP>{ &c, c.N >> 3, S != top, o < (c.N >> 1) });
+    } else if constexpr (S >= Sl) {
+        fn(gl_st(c, S));
+    } else {
+        fn(lds_st(c, S));
+    }
+}
+
+// ls_op for one class: the same calls, with the arm chosen at instantiation (ls_op itself,
+// inlined once per class with literal arguments, gives the same code but has the compiler
+// clone every arm and every storage variant per class before it prunes them: 210 s instead
+// of 75 s for config 3)
+template <int LP, uint32_t CODE, uint32_t S, bool FUSE>
+PCG_DEV void ls_op_lit(Ls<LP>& c, uint32_t o, uint32_t& P, uint32_t desc)
+{
+    [[maybe_unused]] const bool act = c.p < P;
+    if constexpr (CODE == OP_F && FUSE)
+        ls_fgf_op<OP_F>(c, S, o, P);
+    else if constexpr (CODE == OP_F)
+        ls_fg_op<OP_F>(c, S, o, P);
+    else if constexpr (CODE == OP_G && FUSE)
+        ls_fgf_op<OP_G>(c, S, o, P);
+    else if constexpr (CODE == OP_G)
+        ls_fg_op<OP_G>(c, S, o, P);
+    else if constexpr (CODE == OP_COMB)
+        ls_comb(c, S, o, act);
+    else if constexpr (CODE == OP_S_ST8)
+        with_stage_lit<3u>(c, o, [&](auto src) { ls_st8(c, src, desc, o, P); });
+    else if constexpr (CODE == OP_S_R0)
+        with_stage_lit<S>(c, o, [&](auto src) { ls_r0(c, src, S, o, act); });
+    else // OP_S_R1 / OP_S_SPC (n >= 8)
+        with_stage_lit<S>(c, o, [&](auto src) { ls_branch_leaf(c, src, CODE, S, o, P); });
+    wsync();
+}
+
+// the walk's switch on the class id: a balanced tree of wave-uniform compares over
+// [LO, HI), each leaf the op with its class's literals
+template <int LP, uint32_t LO, uint32_t HI>
+PCG_DEV void ls_class_op(Ls<LP>& c, uint32_t cls, uint32_t o, uint32_t& P, uint32_t desc)
+{
+    if constexpr (HI - LO == 1u) {
+        constexpr uint32_t key = rtc_tab.keys[LO];
+        ls_op_lit<LP, ls_class_code(key), ls_class_stage(key), ls_class_fused(key)>(c, o, P, desc);
+    } else {
+        constexpr uint32_t MID = LO + (HI - LO) / 2u;
+        if (cls < MID)
+            ls_class_op<LP, LO, MID>(c, cls, o, P, desc);
+        else
+            ls_class_op<LP, MID, HI>(c, cls, o, P, desc);
+    }
+}
+#endif
 
 template <int LP, uint32_t K>
 PCG_DEV void ls_walk(Ls<LP>& c, uint32_t& P)
@@ -2980,6 +3125,11 @@ PCG_DEV void sclls_body(const KernelArgs& a)
 #endif
 #if defined(PCG_RTC) && PCG_RTC_UNROLL
         ls_walk<LP, 0>(c, P);
+#elif defined(PCG_LS_CLASSES)
+        for (uint32_t kpos = 0; kpos < rtc_tab.npos; ++kpos) {
+            const uint32_t e = rtc_dtab.pos[2u * kpos], desc = rtc_dtab.pos[2u * kpos + 1u];
+            ls_class_op<LP, 0u, rtc_tab.ncls>(c, e & 0xffu, e >> 16, P, desc);
+        }
 #else
         for (uint32_t kop = 0; kop < a.nops; ++kop) {
 #ifdef PCG_LS_PROF
@@ -3320,6 +3470,17 @@ std::string sclls_rtc_defines(bool* nondefault)
     if (nondefault)
         *nondefault = nd;
     return s;
+}
+
+int sclls_rtc_classes(const uint32_t* ops, uint32_t nops, uint32_t log2N, uint32_t Sl, uint32_t virt, uint32_t fuse,
+                      std::vector<uint32_t>* keys, uint32_t* pos)
+{
+    uint32_t k[LS_MAXCLS], nc = 0;
+    const uint32_t np = ls_classify(ops, nops, Sl, ls_mtop(log2N, virt), fuse, k, &nc, pos);
+    if (np == ~0u)
+        return -1;
+    keys->assign(k, k + nc);
+    return (int)np;
 }
 
 static uint32_t lp_of(uint32_t L)

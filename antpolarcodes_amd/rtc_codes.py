@@ -107,6 +107,40 @@ def random_list_codes():
     return out
 
 
+def high_leaf_set(N=1024):
+    """A frozen set of N whose first quarter is frozen: a rate-0 leaf at stage log2(N) - 2, so the
+    list layout does not recompute the quarters (sclls_layout: a leaf at stage >= top - 2); the
+    rest is the Bhattacharyya set of rate 1/2."""
+    from .construction import frozen_bits
+    return sorted(set(range(N // 4)) | {int(v) for v in frozen_bits(N, N // 2, 0.0)})
+
+
+def class_codes():
+    """(N, L, frozen spec, crc, systematic): small list codes at which each branch of the
+    specialised walk's op-class derivation first appears (tests/test_gpu_rtc_classes.py):
+    N = 32 no stage above the LDS limit, 64 stage 3 recomputed, 256 stages in the slab and fused
+    F/G + F, 512 two slab stages under the root's recomputed children (its quarters are stored:
+    sclls_layout recomputes them from N = 1024 on), 1024 with a leaf at stage top - 2 (quarters
+    stored) and without one (quarters recomputed); list sizes 2, 4, 8 and two below their lane
+    count, CRC 0 and 8, systematic and not."""
+    hs = tuple(high_leaf_set(1024))
+    rnd512 = [fr for N, L, fr in random_list_codes() if (N, L) == (512, 8)][0]
+    rnd1024 = [fr for N, L, fr in random_list_codes() if (N, L) == (1024, 4)][0]
+    return [
+        (32, 2, ("BB", 16), 8, True),
+        (32, 8, ("BB", 16), 0, False),
+        (64, 4, ("BB", 32), 0, False),
+        (64, 5, ("BB", 32), 8, True),
+        (256, 8, ("BB", 128), 8, False),
+        (256, 2, ("BB", 128), 0, True),
+        (512, 8, ("set", tuple(rnd512)), 0, True),
+        (512, 6, ("BB", 256), 8, False),
+        (1024, 8, ("set", hs), 8, True),
+        (1024, 4, ("set", hs), 0, False),
+        (1024, 4, ("set", tuple(rnd1024)), 0, True),
+    ]
+
+
 def validation_codes():
     """The codes the GPU parity tests run through specialised kernels (tests/test_gpu_rtc.py,
     tests/test_gpu_char.py and the specialised variants of the full-size parity tests)."""
@@ -123,6 +157,7 @@ def validation_codes():
         out.append((N, L, ("BB", K), crc, sysm))          # list plans
     for N, L, fr in random_list_codes():                  # list plans on random frozen sets
         out.append((N, L, ("set", tuple(fr)), 0, True))
+    out += class_codes()                                  # the specialised walk's op classes
     out.append((1024, 8, ("5G", 512), 0, True))           # config 4's decoder core with the Dummy detector
     out.append((1024, 1, ("5G", 512), 11, True))          # config 4 through Fast-SSC
     for crc in (8, 16, 32):                               # AdaptiveFloat: both stages
