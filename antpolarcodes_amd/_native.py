@@ -96,6 +96,9 @@ def lib():
         L.pcg_plan_set_depthfirst_trials.argtypes = [P, C.c_uint32]
         L.pcg_decode_depthfirst_f32.argtypes = [P, P, C.c_uint64, P, P, P, P, P]
         L.pcg_decode_depthfirst_f32_host.argtypes = [P, P, C.c_uint64, P, P, P, P]
+        L.pcg_plan_create_errorlocator.argtypes = [C.POINTER(P), C.c_uint32, P, C.c_uint32, C.c_int]
+        L.pcg_errorlocator_f32.argtypes = [P, C.c_int, P, P, C.c_uint64, P, P, P, P, P]
+        L.pcg_errorlocator_f32_host.argtypes = [P, C.c_int, P, P, C.c_uint64, P, P, P, P]
         L.pcg_plan_describe.argtypes = [P, C.POINTER(PlanDesc)]
         L.pcg_plan_kernel_name.argtypes = [P]
         L.pcg_plan_kernel_name.restype = C.c_char_p
@@ -443,6 +446,70 @@ class DepthFirstPlan(Plan):
         _check_tensor("trials", trials, torch.uint8, (F,), self.device)
         _check(lib().pcg_decode_depthfirst_f32(self._h, _ptr(llr), F, _ptr(info), _ptr(ok), _ptr(bits),
                                                _ptr(trials), _stream(stream, llr)))
+
+
+EL_MODES = {"reference": 0, "correct": 1, "first": 2}  # PCG_EL_*
+
+
+class ErrorLocatorPlan(Plan):
+    """An error-locator plan (pcg_plan_create_errorlocator): the reference's Decoding::ErrorLocator,
+    plain successive cancellation down to single bits in which a leaf outputs its LLR or a desired
+    value.  Modes: "reference" (no comparison), "correct" (an information bit whose sign differs
+    from its desired value's outputs the desired value: the genie) and "first" (compare only).
+    Outputs: u (F x N float32, getOutput()), bits (F x N uint32, getSoftCodeword), first (int32:
+    the first bit replaced / mismatching, or -1) and count (uint32: bits replaced)."""
+
+    def __init__(self, N, frozen, device=0):
+        fr, fp = _frozen_array(frozen)
+        h = C.c_void_p()
+        _check(lib().pcg_plan_create_errorlocator(C.byref(h), int(N), fp, int(fr.size), int(device)))
+        self._h = h
+        self.N, self.L, self.K = int(N), 1, int(N) - int(fr.size)
+        self.kb = (self.K + 7) // 8
+        self.device = device
+        self.fixed = False
+
+    @staticmethod
+    def _mode(mode):
+        if mode not in EL_MODES:
+            raise ValueError(f"mode {mode!r}: one of {sorted(EL_MODES)}")
+        return EL_MODES[mode]
+
+    def locate_host(self, llr, desired=None, mode="correct", want_u=True, want_bits=False):
+        """Host arrays: returns (u, bits, first, count) (pcg_errorlocator_f32_host); an output not
+        asked for is None.  desired=None: +0 at information bits, +inf at frozen bits."""
+        m = self._mode(mode)
+        llr = np.ascontiguousarray(llr, dtype=np.float32).reshape(-1, self.N)
+        F = llr.shape[0]
+        if desired is not None:
+            desired = np.ascontiguousarray(desired, dtype=np.float32).reshape(-1, self.N)
+            if desired.shape[0] != F:
+                raise ValueError(f"desired: {desired.shape[0]} frames, llr has {F}")
+        u = np.zeros((F, self.N), np.float32) if want_u else None
+        bits = np.zeros((F, self.N), np.uint32) if want_bits else None
+        first, count = np.zeros(F, np.int32), np.zeros(F, np.uint32)
+        _check(lib().pcg_errorlocator_f32_host(self._h, m, llr.ctypes.data,
+                                               None if desired is None else desired.ctypes.data, F,
+                                               *(None if a is None else a.ctypes.data
+                                                 for a in (u, bits, first, count))))
+        return u, bits, first, count
+
+    def locate(self, llr, desired=None, mode="correct", u=None, bits=None, first=None, count=None, stream=None):
+        """Device-resident torch CUDA tensors (pcg_errorlocator_f32): llr and desired float32 F x N,
+        u float32 F x N, bits int32 F x N, first and count int32 F (each output or None)."""
+        import torch
+        m = self._mode(mode)
+        if not hasattr(llr, "shape"):
+            raise ValueError("llr must be a tensor (its first dimension is the frame count)")
+        F = llr.shape[0]
+        _check_tensor("llr", llr, torch.float32, (F, self.N), self.device)
+        _check_tensor("desired", desired, torch.float32, (F, self.N), self.device)
+        _check_tensor("u", u, torch.float32, (F, self.N), self.device)
+        _check_tensor("bits", bits, torch.int32, (F, self.N), self.device)
+        _check_tensor("first", first, torch.int32, (F,), self.device)
+        _check_tensor("count", count, torch.int32, (F,), self.device)
+        _check(lib().pcg_errorlocator_f32(self._h, m, _ptr(llr), _ptr(desired), F, _ptr(u), _ptr(bits),
+                                          _ptr(first), _ptr(count), _stream(stream, llr)))
 
 
 class Puncturer:

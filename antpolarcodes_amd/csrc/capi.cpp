@@ -6,6 +6,7 @@
 #include "plan.hpp"
 #include "rtc.hpp"
 #include "depthfirst.hpp"
+#include "errorlocator.hpp"
 #include "fsscan.hpp"
 #include "scan.hpp"
 
@@ -106,9 +107,19 @@ struct pcg_plan {
     bool depthfirst = false;
     uint32_t df_trials = 1;       // trial limit
     uint32_t df_slab = 0;         // words of state per codeword
-    // SCAN, Fast-SSCAN or SC-Flip: no rtc, no 8-bit, no puncturing
-    bool soft_plan() const { return scan || fsscan || depthfirst; }
-    const char* soft_name() const { return depthfirst ? "SC-Flip" : fsscan ? "Fast-SSCAN" : "SCAN"; }
+    // error-locator plans (pcg_plan_create_errorlocator; errorlocator.hpp): host.ops holds the
+    // SC-Flip schedule; no information bytes, so no decode entry point but pcg_errorlocator_f32
+    bool errloc = false;
+    uint32_t el_slab = 0;         // words of state per codeword
+    // pcg_errorlocator_f32_host staging: llr | desired | u | bits (floats), first | count (words)
+    float* d_el = nullptr;
+    uint64_t el_frames = 0;
+    // SCAN, Fast-SSCAN, SC-Flip or error locator: no rtc, no 8-bit, no puncturing
+    bool soft_plan() const { return scan || fsscan || depthfirst || errloc; }
+    const char* soft_name() const
+    {
+        return errloc ? "error-locator" : depthfirst ? "SC-Flip" : fsscan ? "Fast-SSCAN" : "SCAN";
+    }
 };
 
 // The host-pointer pipeline of pcg_decode_f32_host / pcg_decode_i8_host: chunks of the
@@ -218,6 +229,7 @@ void free_plan_device(pcg_plan* p)
     (void)hipFree(p->d_soft);
     (void)hipFree(p->d_ext);
     (void)hipFree(p->d_trials);
+    (void)hipFree(p->d_el);
     if (p->last_ev)
         (void)hipEventDestroy(p->last_ev);
     p->last_ev = nullptr;
@@ -786,6 +798,8 @@ static int plan_finish(pcg_plan** out, pcg_plan* p, int device)
         p->wave_cap = pcg::fsscan_wave_cap(h.N, p->fss_slab);
     } else if (p->depthfirst) {
         p->wave_cap = pcg::depthfirst_wave_cap(h.N, p->df_slab);
+    } else if (p->errloc) {
+        p->wave_cap = pcg::errorlocator_wave_cap(h.N, p->el_slab);
     } else if (h.fixed && h.L == 1 && h.sc_kind == 0) {
         p->wave_cap = pcg::sccs_wave_cap(p->wave_lds_floats, false);
         p->wave_cap_i8 = pcg::sccs_wave_cap(p->wave_lds_floats, true);
@@ -934,7 +948,7 @@ int pcg_plan_describe(const pcg_plan* p, pcg_plan_desc* d)
     d->info_length = p->host.K;
     d->list_size = p->scan ? p->scan_iters : p->fsscan ? p->fss_trials : p->depthfirst ? p->df_trials : p->host.L;
     d->node_count = p->host.node_count;
-    d->op_count = (uint32_t)p->host.ops.size() / (p->fsscan ? pcg::FSS_WORDS : p->depthfirst ? pcg::DF_WORDS : 1u);
+    d->op_count = (uint32_t)p->host.ops.size() / (p->fsscan ? pcg::FSS_WORDS : (p->depthfirst || p->errloc) ? pcg::DF_WORDS : 1u);
     d->lds_bytes = p->wave_lds_floats * 4;
     d->scratch_bytes = p->scratch_floats * 4;
     d->crc_kind = p->host.crc_kind;
@@ -1149,6 +1163,8 @@ int pcg_decode_f32(pcg_plan* p,
 {
     if (!p)
         return fail(PCG_E_ARG, "null plan");
+    if (p->errloc)
+        return fail(PCG_E_UNSUPPORTED, "error-locator plans produce no information bytes (pcg_errorlocator_f32)");
     if (F == 0)
         return PCG_OK;
     if (!llr || !info)
@@ -1686,6 +1702,8 @@ int pcg_decode_f32_host(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info
 {
     if (!p)
         return fail(PCG_E_ARG, "null plan");
+    if (p->errloc)
+        return fail(PCG_E_UNSUPPORTED, "error-locator plans produce no information bytes (pcg_errorlocator_f32)");
     if (F == 0)
         return PCG_OK;
     if (!llr || !info)
@@ -1706,7 +1724,7 @@ static int soft_supported(const pcg_plan* p)
 {
     if (!p)
         return fail(PCG_E_ARG, "null plan");
-    if (p->host.L != 1 || p->host.fixed || p->fast || p->depthfirst)
+    if (p->host.L != 1 || p->host.fixed || p->fast || p->depthfirst || p->errloc)
         return fail(PCG_E_UNSUPPORTED, "soft codewords: Fast-SSC float plans only (FastSscAvxFloat)");
     if (pcg::sc_soft_lds_bytes(p->host.N) == 0)
         return fail(PCG_E_UNSUPPORTED, "soft codewords: block length too large for one wave's LDS");
@@ -2235,6 +2253,160 @@ int pcg_decode_depthfirst_f32_host(pcg_plan* p,
                                                          bits ? reinterpret_cast<uint32_t*>(p->d_soft) : nullptr,
                                                          static_cast<uint8_t*>(d_x), nullptr);
                             });
+}
+
+int pcg_plan_create_errorlocator(pcg_plan** out, uint32_t N, const uint32_t* frozen, uint32_t n_frozen, int device)
+{
+    if (!out)
+        return fail(PCG_E_ARG, "plan output pointer is null");
+    *out = nullptr;
+    auto* p = new pcg_plan();
+    std::string err;
+    const int rc = pcg::build_errorlocator_plan(p->host, N, frozen, n_frozen, &p->el_slab, &err);
+    if (rc != 0) {
+        delete p;
+        return fail(rc, err);
+    }
+    p->errloc = true;
+    p->host.sc_kind = 0;
+    p->rtc_mode = 0;
+    p->kernel = "errorlocator_kernel";
+    p->wave_lds_floats = pcg::errorlocator_lds_bytes(N) / 4u;
+    p->scratch_floats = p->el_slab; // per codeword
+    return plan_finish(out, p, device);
+}
+
+// ErrorLocator::decode / decodeFindFirstError (errorlocator.cpp:214-232) over F frames: one launch
+// of errorlocator_kernel
+static int run_errorlocator(pcg_plan* p, int mode, const float* llr, const float* desired, uint64_t F, float* u,
+                            uint32_t* bits, int32_t* first, uint32_t* count, void* stream)
+{
+    const auto& h = p->host;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    pcg::ErrorLocatorArgs a{};
+    a.llr = llr;
+    a.desired = desired;
+    a.F = F;
+    a.ops = p->d_ops;
+    a.nops = (uint32_t)h.ops.size() / pcg::DF_WORDS;
+    a.N = h.N;
+    a.mode = (uint32_t)mode;
+    a.u = u;
+    a.bits = bits;
+    a.first = first;
+    a.count = count;
+    a.slab_floats = p->el_slab;
+    int rc = order_on(p, s);
+    if (rc != 0)
+        return rc;
+    a.units = (uint32_t)pcg::wave_units(F, 64, p->wave_cap);
+    if ((rc = grow_scratch(p, a.units, sizeof(float), s, 64ull * p->el_slab)) != 0)
+        return rc;
+    a.slab = p->d_scratch;
+    if ((rc = pcg::launch_errorlocator(a, s)) != 0)
+        return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return mark_done(p, s);
+}
+
+static int errorlocator_args(const pcg_plan* p, int mode, const float* llr, uint64_t F)
+{
+    if (!p)
+        return fail(PCG_E_ARG, "null plan");
+    if (!p->errloc)
+        return fail(PCG_E_ARG, "not an error-locator plan (pcg_plan_create_errorlocator)");
+    if (mode != PCG_EL_REFERENCE && mode != PCG_EL_CORRECT && mode != PCG_EL_FIRST)
+        return fail(PCG_E_ARG, "error locator: unknown mode");
+    if (!llr)
+        return fail(PCG_E_ARG, "null llr buffer");
+    if (F > 0xFFFFFFFFull)
+        return fail(PCG_E_ARG, "at most 2^32 - 1 frames per call");
+    return PCG_OK;
+}
+
+int pcg_errorlocator_f32(pcg_plan* p,
+                         int mode,
+                         const float* llr,
+                         const float* desired,
+                         uint64_t F,
+                         float* u,
+                         uint32_t* bits,
+                         int32_t* first,
+                         uint32_t* count,
+                         void* stream)
+{
+    const int rc = errorlocator_args(p, mode, llr, F);
+    if (rc != 0)
+        return rc;
+    if (F == 0)
+        return PCG_OK;
+    if (p->device < 0)
+        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
+    DeviceGuard g(p->device);
+    return run_errorlocator(p, mode, llr, desired, F, u, bits, first, count, stream);
+}
+
+int pcg_errorlocator_f32_host(pcg_plan* p,
+                              int mode,
+                              const float* llr,
+                              const float* desired,
+                              uint64_t F,
+                              float* u,
+                              uint32_t* bits,
+                              int32_t* first,
+                              uint32_t* count)
+{
+    int rc = errorlocator_args(p, mode, llr, F);
+    if (rc != 0)
+        return rc;
+    if (F == 0)
+        return PCG_OK;
+    if (p->device < 0)
+        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
+    DeviceGuard g(p->device);
+    // chunks of pcg_decode_f32_host's size through staging kept in the plan (4 N + 2 words a frame)
+    const uint64_t N = p->host.N;
+    uint64_t chunk = (uint64_t)env_int("PCG_HOST_CHUNK", 0);
+    if (chunk == 0)
+        chunk = std::min<uint64_t>(65536, std::max<uint64_t>(4096, (64ull << 20) / (N * sizeof(float))));
+    chunk = std::min<uint64_t>(chunk, F);
+    if ((rc = order_on(p, nullptr)) != 0)
+        return rc;
+    hipError_t e;
+    if (p->el_frames < chunk) {
+        if ((e = hipStreamSynchronize(nullptr)) != hipSuccess)
+            return hip_fail(e, "hipStreamSynchronize");
+        (void)hipFree(p->d_el);
+        p->d_el = nullptr;
+        p->el_frames = 0;
+        if ((e = hipMalloc(&p->d_el, chunk * (4 * N + 2) * sizeof(float))) != hipSuccess)
+            return hip_fail(e, "hipMalloc(error-locator staging)");
+        p->el_frames = chunk;
+    }
+    float* d_llr = p->d_el;
+    float* d_des = d_llr + chunk * N;
+    float* d_u = d_des + chunk * N;
+    uint32_t* d_bits = reinterpret_cast<uint32_t*>(d_u + chunk * N);
+    int32_t* d_first = reinterpret_cast<int32_t*>(d_bits + chunk * N);
+    uint32_t* d_count = reinterpret_cast<uint32_t*>(d_first + chunk);
+    for (uint64_t f0 = 0; f0 < F; f0 += chunk) {
+        const uint64_t n = std::min(chunk, F - f0);
+        if ((e = hipMemcpy(d_llr, llr + f0 * N, n * N * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess ||
+            (desired &&
+             (e = hipMemcpy(d_des, desired + f0 * N, n * N * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess))
+            return hip_fail(e, "hipMemcpy(H2D)");
+        if ((rc = run_errorlocator(p, mode, d_llr, desired ? d_des : nullptr, n, u ? d_u : nullptr,
+                                   bits ? d_bits : nullptr, first ? d_first : nullptr, count ? d_count : nullptr,
+                                   nullptr)) != 0)
+            return rc;
+        if ((u && (e = hipMemcpy(u + f0 * N, d_u, n * N * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) ||
+            (bits && (e = hipMemcpy(bits + f0 * N, d_bits, n * N * 4, hipMemcpyDeviceToHost)) != hipSuccess) ||
+            (first && (e = hipMemcpy(first + f0, d_first, n * 4, hipMemcpyDeviceToHost)) != hipSuccess) ||
+            (count && (e = hipMemcpy(count + f0, d_count, n * 4, hipMemcpyDeviceToHost)) != hipSuccess))
+            return hip_fail(e, "hipMemcpy(D2H)");
+        if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) // no output asked for: still synchronous
+            return hip_fail(e, "hipStreamSynchronize");
+    }
+    return PCG_OK;
 }
 
 void pcg_plan_destroy(pcg_plan* p)

@@ -4,6 +4,7 @@
 #include <polarcode/construction/constructor.h>
 #include <polarcode/decoding/decoder.h>
 #include <polarcode/decoding/depth_first.h>
+#include <polarcode/decoding/errorlocator.h>
 #include <polarcode/decoding/fastsscan_float.h>
 #include <polarcode/decoding/scan.h>
 #include <polarcode/encoding/butterfly_fip_packed.h>
@@ -1284,6 +1285,121 @@ void DepthFirst::decodeBatchBitsDevice(const float* llr, size_t F, uint8_t* info
 void DepthFirst::decodeBatchDevice(const float* llr, size_t F, uint8_t* info, uint8_t* ok, float*, void* hipStream)
 {
     decodeBatchBitsDevice(llr, F, info, ok, nullptr, nullptr, hipStream);
+}
+
+// ---- ErrorLocator (errorlocator.cpp): the genie-aided SC error locator on the GPU ---------------
+ErrorLocator::ErrorLocator(unsigned blockLength, const std::vector<unsigned>& frozenBits, int device)
+    : mDevice(device)
+{
+    initialize(blockLength, frozenBits);
+}
+
+ErrorLocator::~ErrorLocator() { releasePlan(); }
+
+void ErrorLocator::releasePlan()
+{
+    if (mPlan)
+        pcg_plan_destroy(mPlan);
+    mPlan = nullptr;
+}
+
+void ErrorLocator::clear() { releasePlan(); }
+
+// errorlocator.cpp:192-210: float input and output containers; a fresh tree, so the defaults
+void ErrorLocator::initialize(size_t blockLength, const std::vector<unsigned>& frozenBits)
+{
+    if (mBlockLength == blockLength && mBlockLength != 0 && frozenBits == mFrozenBits)
+        return;
+    pcg_plan* probe = nullptr; // validate now, without a GPU
+    const int rc = pcg_plan_create_errorlocator(&probe, (uint32_t)blockLength, frozenBits.data(),
+                                                (uint32_t)frozenBits.size(), -1);
+    if (rc != 0)
+        throw_pcg(rc);
+    pcg_plan_destroy(probe);
+    Decoder::initialize(blockLength, frozenBits);
+    releasePlan();
+    if (!mExternalContainers) {
+        delete mLlrContainer;
+        delete mBitContainer;
+        delete[] mOutputContainer;
+    }
+    mExternalContainers = false;
+    mLlrContainer = new FloatContainer(mBlockLength, mFrozenBits);
+    mBitContainer = new FloatContainer(mBlockLength, mFrozenBits);
+    mOutputContainer = new unsigned char[(mBlockLength + 7) / 8]();
+    mDesired.clear();
+    mOutput.assign(mBlockLength, 0.0f);
+}
+
+void ErrorLocator::ensurePlan()
+{
+    if (mPlan)
+        return;
+    const int rc = pcg_plan_create_errorlocator(&mPlan, (uint32_t)mBlockLength, mFrozenBits.data(),
+                                                (uint32_t)mFrozenBits.size(), mDevice);
+    if (rc != 0) {
+        mPlan = nullptr;
+        throw_pcg(rc);
+    }
+}
+
+void ErrorLocator::setAsReferenceDecoder() { mIsReferenceDecoder = true; }
+
+void ErrorLocator::setDesiredOutput(std::vector<float> desired)
+{
+    if (desired.size() < mBlockLength)
+        throw std::logic_error("setDesiredOutput: fewer values than the block length");
+    mDesired.assign(desired.begin(), desired.begin() + mBlockLength);
+}
+
+std::vector<float> ErrorLocator::getOutput() { return mOutput; }
+
+int ErrorLocator::firstError() { return mFirstError; }
+
+int ErrorLocator::correctionCount() { return mCorrectionCount; }
+
+int ErrorLocator::run(int mode)
+{
+    ensurePlan();
+    int32_t first = -1;
+    uint32_t count = 0;
+    const int rc = pcg_errorlocator_f32_host(
+        mPlan, mode, static_cast<FloatContainer*>(mLlrContainer)->data(), mDesired.empty() ? nullptr : mDesired.data(),
+        1, mOutput.data(), reinterpret_cast<uint32_t*>(static_cast<FloatContainer*>(mBitContainer)->data()), &first,
+        &count);
+    if (rc != 0)
+        throw_pcg(rc);
+    if (mode != PCG_EL_REFERENCE) { // prepare() (:250-257) runs only in the other two
+        mFirstError = first;
+        mCorrectionCount = (int)count;
+    }
+    return first;
+}
+
+bool ErrorLocator::decode()
+{
+    run(mIsReferenceDecoder ? PCG_EL_REFERENCE : PCG_EL_CORRECT);
+    return true;
+}
+
+int ErrorLocator::decodeFindFirstError() { return run(PCG_EL_FIRST); }
+
+void ErrorLocator::locateBatch(Mode mode, const float* llr, const float* desired, size_t F, float* u, uint32_t* bits,
+                               int32_t* first, uint32_t* count)
+{
+    ensurePlan();
+    const int rc = pcg_errorlocator_f32_host(mPlan, (int)mode, llr, desired, F, u, bits, first, count);
+    if (rc != 0)
+        throw_pcg(rc);
+}
+
+void ErrorLocator::locateBatchDevice(Mode mode, const float* llr, const float* desired, size_t F, float* u,
+                                     uint32_t* bits, int32_t* first, uint32_t* count, void* hipStream)
+{
+    ensurePlan();
+    const int rc = pcg_errorlocator_f32(mPlan, (int)mode, llr, desired, F, u, bits, first, count, hipStream);
+    if (rc != 0)
+        throw_pcg(rc);
 }
 
 Decoder* makeDecoder(size_t blockLength, size_t listSize, const std::vector<unsigned>& frozenBits, int impl)

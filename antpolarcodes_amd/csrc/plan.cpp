@@ -3,6 +3,7 @@
 
 #include "crc_host.hpp"
 #include "depthfirst.hpp"
+#include "errorlocator.hpp"
 #include "fsscan.hpp"
 #include "scan.hpp"
 
@@ -481,12 +482,12 @@ int build_impl(PlanHost& p,
                int crc_kind,
                std::string* err,
                int fixed,
-               int scan, // 1 = SCAN, 2 = Fast-SSCAN, 3 = SC-Flip (DepthFirst)
+               int scan, // 1 = SCAN, 2 = Fast-SSCAN, 3 = SC-Flip (DepthFirst), 4 = the error locator
                uint32_t* slab_floats = nullptr,
                uint32_t trial_limit = 1)
 {
     p = PlanHost();
-    const std::string who = scan == 3 ? "SC-Flip" : scan == 2 ? "Fast-SSCAN" : "SCAN";
+    const std::string who = scan == 4 ? "error locator" : scan == 3 ? "SC-Flip" : scan == 2 ? "Fast-SSCAN" : "SCAN";
     if (scan && (N < 8 || (N & (N - 1)))) {
         *err = who + ": block length must be a power of two >= 8";
         return -1;
@@ -535,6 +536,10 @@ int build_impl(PlanHost& p,
             return -1;
         }
     }
+    if (scan == 4 && nf >= N) {
+        *err = "error locator: needs at least one information bit";
+        return -1;
+    }
     p.N = N;
     p.L = L;
     p.log2N = ilog2(N);
@@ -550,13 +555,13 @@ int build_impl(PlanHost& p,
         p.sc_kind = (k && std::string(k) == "wave") ? 1 : ((k && std::string(k) == "scs") ? 0 : 2);
     }
     try {
-        if (scan == 3) {
+        if (scan == 3 || scan == 4) { // the error locator walks the SC-Flip schedule
             std::vector<uint8_t> isf(N, 0);
             for (uint32_t v : p.frozen)
                 isf[v] = 1;
             uint32_t rank = 0;
             depthfirst_emit(p, isf, N, 0, 0, &rank);
-            *slab_floats = df_slab_floats(N, p.K);
+            *slab_floats = scan == 4 ? el_slab_floats(N) : df_slab_floats(N, p.K);
         } else if (scan == 2) {
             uint32_t top = fsscan_er(N);
             fsscan_emit(p, p.frozen, N, 0, 0, fsscan_el(N), &top);
@@ -691,6 +696,16 @@ int build_depthfirst_plan(PlanHost& p,
                           std::string* err)
 {
     return build_impl(p, N, 1, frozen, nf, systematic, crc_kind, err, 0, 3, slab_floats, trial_limit);
+}
+
+int build_errorlocator_plan(PlanHost& p,
+                            uint32_t N,
+                            const uint32_t* frozen,
+                            uint32_t nf,
+                            uint32_t* slab_floats,
+                            std::string* err)
+{
+    return build_impl(p, N, 1, frozen, nf, 1, 0, err, 0, 4, slab_floats);
 }
 
 } // namespace pcg

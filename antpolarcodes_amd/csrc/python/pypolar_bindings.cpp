@@ -10,6 +10,7 @@
 #include <polarcode/construction/constructor.h>
 #include <polarcode/decoding/decoder.h>
 #include <polarcode/decoding/depth_first.h>
+#include <polarcode/decoding/errorlocator.h>
 #include <polarcode/decoding/fastsscan_float.h>
 #include <polarcode/decoding/scan.h>
 #include <polarcode/encoding/butterfly_fip_packed.h>
@@ -528,6 +529,103 @@ PYBIND11_MODULE(_pypolar, m)
             },
             py::arg("llr_ptr"), py::arg("frames"), py::arg("info_ptr"), py::arg("ok_ptr") = 0,
             py::arg("bits_ptr") = 0, py::arg("trials_ptr") = 0, py::arg("stream") = 0);
+
+    // the reference's Decoding::ErrorLocator (errorlocator.h); its pypolar does not bind the class,
+    // so the names follow the C++ methods
+    py::class_<Decoding::ErrorLocator>(m, "ErrorLocator")
+        .def(py::init([](size_t N, std::vector<unsigned> frozen) {
+                 return std::make_unique<Decoding::ErrorLocator>((unsigned)N, frozen);
+             }),
+             py::arg("blockLength"), py::arg("frozenBitPositions"))
+        .def("blockLength", [](Decoding::ErrorLocator& s) { return s.blockLength(); })
+        .def("infoLength", [](Decoding::ErrorLocator& s) { return s.infoLength(); })
+        .def("frozenBits", [](Decoding::ErrorLocator& s) { return s.frozenBits(); })
+        .def("setAsReferenceDecoder", &Decoding::ErrorLocator::setAsReferenceDecoder)
+        .def("firstError", &Decoding::ErrorLocator::firstError)
+        .def("correctionCount", &Decoding::ErrorLocator::correctionCount)
+        .def("setDesiredOutput",
+             [](Decoding::ErrorLocator& s, const f32array& a) {
+                 py::buffer_info in = a.request();
+                 if (in.ndim != 1 || (size_t)in.size != s.blockLength())
+                     throw std::runtime_error("setDesiredOutput expects blockLength float32 values");
+                 const float* p = static_cast<const float*>(in.ptr);
+                 s.setDesiredOutput(std::vector<float>(p, p + in.size));
+             })
+        .def("getOutput",
+             [](Decoding::ErrorLocator& s) {
+                 const std::vector<float> v = s.getOutput();
+                 py::array_t<float> out(v.size());
+                 std::memcpy(out.mutable_data(), v.data(), v.size() * sizeof(float));
+                 return out;
+             })
+        .def("getSoftCodeword",
+             [](Decoding::ErrorLocator& s) {
+                 py::array_t<float> out(s.blockLength());
+                 s.getSoftCodeword(out.mutable_data());
+                 return out;
+             })
+        .def("decode_vector",
+             [](Decoding::ErrorLocator& s, const f32array& a) {
+                 py::buffer_info in = a.request();
+                 if (in.ndim != 1)
+                     throw std::runtime_error("Only ONE-dimensional vectors allowed!");
+                 if ((size_t)in.size != s.blockLength())
+                     throw std::runtime_error("Input vector size != blockSize!");
+                 s.setSignal(static_cast<const float*>(in.ptr));
+                 return s.decode(); // always true; the decoder produces no information bytes
+             })
+        .def("decodeFindFirstError",
+             [](Decoding::ErrorLocator& s, const f32array& a) {
+                 py::buffer_info in = a.request();
+                 if (in.ndim != 1)
+                     throw std::runtime_error("Only ONE-dimensional vectors allowed!");
+                 if ((size_t)in.size != s.blockLength())
+                     throw std::runtime_error("Input vector size != blockSize!");
+                 s.setSignal(static_cast<const float*>(in.ptr));
+                 return s.decodeFindFirstError();
+             })
+        .def(
+            "locate_batch",
+            [](Decoding::ErrorLocator& s, const f32array& a, py::object desired, std::string mode, bool return_u,
+               bool return_bits) {
+                py::buffer_info in = a.request();
+                const size_t N = s.blockLength();
+                if (in.ndim != 2 || (size_t)in.shape[1] != N)
+                    throw std::runtime_error("locate_batch expects a (frames, blockLength) float32 array");
+                const size_t F = (size_t)in.shape[0];
+                Decoding::ErrorLocator::Mode md;
+                if (mode == "reference")
+                    md = Decoding::ErrorLocator::Reference;
+                else if (mode == "correct")
+                    md = Decoding::ErrorLocator::Correct;
+                else if (mode == "first")
+                    md = Decoding::ErrorLocator::First;
+                else
+                    throw std::runtime_error("locate_batch: mode is \"reference\", \"correct\" or \"first\"");
+                f32array des;
+                const float* dp = nullptr;
+                if (!desired.is_none()) {
+                    des = desired.cast<f32array>();
+                    py::buffer_info di = des.request();
+                    if (di.ndim != 2 || (size_t)di.shape[0] != F || (size_t)di.shape[1] != N)
+                        throw std::runtime_error("locate_batch: desired must have the shape of the frames");
+                    dp = static_cast<const float*>(di.ptr);
+                }
+                py::array_t<float> u({ return_u ? F : 0, N });
+                py::array_t<uint32_t> bits({ return_bits ? F : 0, N });
+                py::array_t<int32_t> first(F);
+                py::array_t<uint32_t> count(F);
+                {
+                    py::gil_scoped_release nogil;
+                    s.locateBatch(md, static_cast<const float*>(in.ptr), dp, F, return_u ? u.mutable_data() : nullptr,
+                                  return_bits ? bits.mutable_data() : nullptr, first.mutable_data(),
+                                  count.mutable_data());
+                }
+                return py::make_tuple(return_u ? py::object(u) : py::none(),
+                                      return_bits ? py::object(bits) : py::none(), first, count);
+            },
+            py::arg("llrs"), py::arg("desired") = py::none(), py::arg("mode") = "correct", py::arg("return_u") = true,
+            py::arg("return_bits") = false);
 
     py::class_<PyEncoder>(m, "PolarEncoder")
         .def(py::init([](size_t N, std::vector<unsigned> frozen) {

@@ -20,14 +20,19 @@ reports the passes run).
 DepthFirstDecoder(blockLength, trialLimit, frozenBitPositions) is the reference's SC-Flip decoder
 (Decoding::DepthFirst): plain successive cancellation, decoded again with the least reliable
 information-bit decisions flipped while the detector check fails (decode_batch(...,
-return_bits=True, return_trials=True) returns the decoded words and the trials run).  The native module is mandatory: there is no CPU fallback.
+return_bits=True, return_trials=True) returns the decoded words and the trials run).
+ErrorLocator(blockLength, frozenBitPositions) is the reference's genie-aided SC error locator
+(Decoding::ErrorLocator, which the reference's pypolar does not bind: the names are its C++ methods'):
+decode_vector, setDesiredOutput, setAsReferenceDecoder, getOutput, firstError, correctionCount,
+decodeFindFirstError, and locate_batch(llrs, desired=None, mode="correct") -> (u, bits, first, count).
+The native module is mandatory: there is no CPU fallback.
 """
 from ._native import _prefer_torch_hip_runtime
 
 _prefer_torch_hip_runtime()  # share PyTorch's HIP runtime (see _native.py)
 
-from ._pypolar import (DepthFirstDecoder, Detector, FastSscanDecoder, PolarDecoder, PolarEncoder, Puncturer, ScanDecoder,  # noqa: E402
+from ._pypolar import (DepthFirstDecoder, Detector, ErrorLocator, FastSscanDecoder, PolarDecoder, PolarEncoder, Puncturer, ScanDecoder,  # noqa: E402
                        frozen_bits)
 
 __all__ = ["PolarDecoder", "PolarEncoder", "Detector", "Puncturer", "ScanDecoder", "FastSscanDecoder",
-           "DepthFirstDecoder", "frozen_bits"]
+           "DepthFirstDecoder", "ErrorLocator", "frozen_bits"]

@@ -45,7 +45,12 @@
  *   pcg_plan_set_depthfirst_trials <- the trial limit of later decodes
  *   pcg_decode_depthfirst_f32[_host] <- DepthFirst::decode :599-638 (Manager::decode :28-82,
  *                        decodeNext :85-153, RateRNode::decode :277-284), batched
- *   pcg_plan_destroy  <- Decoder::~Decoder decoder.cpp:104-114
+ *   pcg_plan_create_errorlocator <- new Decoding::ErrorLocator(N, frozen)
+ *                        (src/polarcode/decoding/errorlocator.cpp:176-210, createDecoder :156-172)
+ *   pcg_errorlocator_f32[_host] <- ErrorLocator::decode :214-225 (as the reference decoder or
+ *                        with the genie's corrections), decodeFindFirstError :227-232, getOutput,
+ *                        firstError, correctionCount, batched
+ *   pcg_plan_destroy <- Decoder::~Decoder decoder.cpp:104-114
  *   pcg_last_error    <- the std::exception text the reference throws
  *   pcg_puncturer_*   <- PolarCode::Puncturer (include/polarcode/puncturer.h:33-99,
  *                        src/polarcode/puncturer.cpp:51-89): depuncture / puncture /
@@ -414,6 +419,64 @@ int pcg_decode_depthfirst_f32_host(pcg_plan* plan,
                                    uint8_t* ok,
                                    uint32_t* bits,
                                    uint8_t* trials);
+
+/* ---- The genie-aided SC error locator ("bad bit finder") --------------------------------------
+ * (Decoding::ErrorLocator, errorlocator.cpp.)  Plain successive cancellation down to single bits
+ * in which a leaf outputs either its LLR or a DESIRED value, as a whole 32-bit float.  A frozen
+ * leaf always outputs its desired value.  `desired` is F x N floats, all N positions honoured
+ * (setDesiredOutput); NULL means the reference's defaults, +0.0f at information bits and +inf at
+ * frozen bits.  Only the SIGN BITS of the desired values at information bits are compared (a
+ * signed zero counts).  The mode is fixed per call:
+ *   PCG_EL_REFERENCE  setAsReferenceDecoder() + decode(): no comparison; first = -1, count = 0.
+ *   PCG_EL_CORRECT    decode(): every information bit whose sign differs from its desired value's
+ *                     outputs the desired value instead.  first = index (among all N bits) of the
+ *                     first bit replaced or -1 (firstError()), count = bits replaced
+ *                     (correctionCount()).  The reference repeats the root decode once per
+ *                     replacement; SC is causal, so its final state equals ONE decode that
+ *                     compares and replaces each leaf when it is reached, which is what runs here.
+ *   PCG_EL_FIRST      decodeFindFirstError(): compare, never replace.  first = index of the first
+ *                     mismatch or -1; count = 0.
+ * Outputs, each may be NULL and one not asked for costs no stores: u (F x N floats, getOutput():
+ * an LLR, a desired value, or +inf), bits (F x N 32-bit words, getSoftCodeword: the leaf words
+ * XOR-combined upwards), first (F x int32), count (F x uint32).  Every value equals the
+ * reference's bit for bit.  Contract: finite LLRs whose sums stay finite.  N: a power of two,
+ * 8 <= N <= 4096 (PCG_E_UNSUPPORTED above); any strictly ascending frozen set that leaves at least
+ * one information bit.  The decoder produces no information bytes and has no detector.
+ * pcg_plan_describe reports lds_bytes of a wave, node_count / op_count as the SC-Flip plan of the
+ * same code, and scratch_bytes per codeword = 4 * 4 N: the node inputs per level (2 N words), the
+ * decoded words (N) and the desired / leaf values (N).  pcg_plan_kernel_name is
+ * "errorlocator_kernel".  On such a plan pcg_decode_f32[_host], pcg_decode_f32_soft[_host],
+ * pcg_decode_i8[_host], pcg_decode_punctured_f32 and pcg_plan_specialize[_async] return
+ * PCG_E_UNSUPPORTED, the SCAN, Fast-SSCAN and SC-Flip entry points PCG_E_ARG. */
+#define PCG_EL_REFERENCE 0
+#define PCG_EL_CORRECT 1
+#define PCG_EL_FIRST 2
+
+int pcg_plan_create_errorlocator(pcg_plan** plan, uint32_t N, const uint32_t* frozen, uint32_t n_frozen, int device);
+
+/* Run F frames through an error-locator plan.  Device pointers, asynchronous, stream-ordered like
+ * pcg_decode_f32.  PCG_E_ARG for an unknown mode, a NULL llr or any other plan. */
+int pcg_errorlocator_f32(pcg_plan* plan,
+                         int mode,
+                         const float* llr,
+                         const float* desired,
+                         uint64_t F,
+                         float* u,
+                         uint32_t* bits,
+                         int32_t* first,
+                         uint32_t* count,
+                         void* stream);
+
+/* Same with HOST pointers; synchronous.  Streams the batch through device buffers in chunks. */
+int pcg_errorlocator_f32_host(pcg_plan* plan,
+                              int mode,
+                              const float* llr,
+                              const float* desired,
+                              uint64_t F,
+                              float* u,
+                              uint32_t* bits,
+                              int32_t* first,
+                              uint32_t* count);
 
 int pcg_plan_describe(const pcg_plan* plan, pcg_plan_desc* desc);
 
