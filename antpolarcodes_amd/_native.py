@@ -123,6 +123,9 @@ def lib():
         L.pcg_encoder_destroy.restype = None
         L.pcg_random_info.argtypes = [P, C.c_uint64, C.c_uint32, C.c_uint64, P]
         L.pcg_bpsk_awgn_f32.argtypes = [P, C.c_uint64, C.c_uint32, C.c_float, C.c_uint64, P, P]
+        L.pcg_ask_constants.argtypes = [C.c_uint32, P, P]
+        L.pcg_ask_channel_f32.argtypes = [P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float,
+                                          C.c_uint64, P, P, P]
         _lib = L
     return _lib
 
@@ -586,3 +589,34 @@ def random_info_device(info, K, seed, stream=None):
 def bpsk_awgn_device(code, n, sigma, seed, llr, stream=None):
     _check(lib().pcg_bpsk_awgn_f32(_ptr(code), code.shape[0], int(n), float(sigma), int(seed) & (2**64 - 1),
                                    _ptr(llr), _stream(stream, code)))
+
+
+FADINGS = {"awgn": 0, "rayleigh": 1}  # PCG_FADING_NONE, PCG_FADING_RAYLEIGH
+
+
+def ask_constants(bps):
+    """(normal magnitude, power normaliser) of Ask::setBitsPerSymbol (pcg_ask_constants); no device."""
+    nm, pn = C.c_float(), C.c_float()
+    _check(lib().pcg_ask_constants(int(bps), C.byref(nm), C.byref(pn)))
+    return np.float32(nm.value), np.float32(pn.value)
+
+
+def ask_channel_device(code, n, bps, sigma, gain, seed, out, symbols=None, fading="awgn", stream=None):
+    """ASK modulate / AWGN or Rayleigh / demodulate / scale in one launch (pcg_ask_channel_f32).
+    code: F x n/8 uint8, out: F x n float32, symbols (optional): F x ceil(n / bps) float32 receiving
+    the channel output; all on one device.  A shape mismatch would let the kernel read or write out
+    of bounds, so tensors are checked."""
+    if fading not in FADINGS:
+        raise ValueError(f"fading: {fading!r}, expected one of {sorted(FADINGS)}")
+    import torch
+    n, bps, F = int(n), int(bps), code.shape[0]
+    if n <= 0 or n % 8:
+        raise ValueError(f"n: {n}, expected a positive multiple of 8")
+    if not 1 <= bps <= 16:
+        raise ValueError(f"bps: {bps}, expected 1 .. 16")
+    dev = code.device.index if code.device.index is not None else torch.cuda.current_device()
+    _check_tensor("code", code, torch.uint8, (F, n // 8), dev)
+    _check_tensor("out", out, torch.float32, (F, n), dev)
+    _check_tensor("symbols", symbols, torch.float32, (F, -(-n // bps)), dev)
+    _check(lib().pcg_ask_channel_f32(_ptr(code), F, n, bps, FADINGS[fading], float(sigma), float(gain),
+                                     int(seed) & (2**64 - 1), _ptr(out), _ptr(symbols), _stream(stream, code)))

@@ -35,6 +35,14 @@ int launch_compact_failed(const uint8_t* ok, uint64_t F, uint32_t* fmap, uint32_
 int launch_random_info(uint8_t* info, uint64_t F, uint32_t K, uint64_t seed, hipStream_t s);
 int launch_bpsk_awgn(const uint8_t* code, uint64_t F, uint32_t n, float sigma, uint64_t seed, float* llr,
                      hipStream_t s);
+// channel_kernel.hip: ASK modulate / AWGN or Rayleigh / demodulate / scale; nm, pn from ask_constants
+int launch_ask_channel(const uint8_t* code, uint64_t F, uint32_t n, uint32_t bits_per_symbol, bool rayleigh,
+                       float sigma, float gain, float nm, float pn, uint64_t seed, float* out, float* symbols,
+                       hipStream_t s);
+
+// Ask::setBitsPerSymbol (ask.cpp:27-45): mNormalMagnitude and mPowerNormalizer of a normalised
+// constellation, the power summed in float as there.
+void ask_constants(uint32_t bits_per_symbol, float* nm, float* pn);
 
 // Puncturer(E, frozen) (puncturer.cpp:51-66) on the host: parent length and kept positions.
 // Returns 0, or -1 with *err set (the reference's std::out_of_range text).

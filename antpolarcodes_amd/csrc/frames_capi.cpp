@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <random>
 #include <string>
@@ -84,6 +85,16 @@ int build_puncturer(uint32_t E, const uint32_t* frozen, uint32_t nf, uint32_t* N
     }
     *N = parent;
     return 0;
+}
+
+void ask_constants(uint32_t bits_per_symbol, float* nm, float* pn)
+{
+    float power = 0.0f;
+    const float limit = (float)(1u << bits_per_symbol);
+    for (float symbol = 1.0f; symbol < limit; symbol += 2.0f)
+        power += symbol * symbol; // in float: past 2^24 (b >= 9) the rounding is part of the value
+    *nm = (float)std::sqrt(2.0 * power / limit);
+    *pn = (float)(1.0 / *nm);
 }
 
 } // namespace pcg
@@ -418,6 +429,37 @@ int pcg_bpsk_awgn_f32(const uint8_t* code, uint64_t F, uint32_t n, float sigma, 
         return set_error(PCG_E_ARG, "symbols per frame must be a positive multiple of 8");
     if (pcg::launch_bpsk_awgn(code, F, n, sigma, seed, llr, reinterpret_cast<hipStream_t>(stream)))
         return hip_error(hipGetLastError(), "bpsk_awgn launch");
+    return PCG_OK;
+}
+
+int pcg_ask_constants(uint32_t bits_per_symbol, float* normal_magnitude, float* power_normalizer)
+{
+    if (bits_per_symbol < 1 || bits_per_symbol > 16)
+        return set_error(PCG_E_ARG, "bits per symbol must be in [1, 16]");
+    if (!normal_magnitude || !power_normalizer)
+        return set_error(PCG_E_ARG, "null output pointer");
+    pcg::ask_constants(bits_per_symbol, normal_magnitude, power_normalizer);
+    return PCG_OK;
+}
+
+int pcg_ask_channel_f32(const uint8_t* code, uint64_t F, uint32_t n, uint32_t bits_per_symbol, int fading,
+                        float sigma, float gain, uint64_t seed, float* out, float* symbols, void* stream)
+{
+    if (bits_per_symbol < 1 || bits_per_symbol > 16)
+        return set_error(PCG_E_ARG, "bits per symbol must be in [1, 16]");
+    if (fading != PCG_FADING_NONE && fading != PCG_FADING_RAYLEIGH)
+        return set_error(PCG_E_ARG, "unknown fading (PCG_FADING_NONE, PCG_FADING_RAYLEIGH)");
+    if (F == 0)
+        return PCG_OK;
+    if (!code || !out)
+        return set_error(PCG_E_ARG, "null buffer");
+    if (n == 0 || n % 8)
+        return set_error(PCG_E_ARG, "code bits per frame must be a positive multiple of 8");
+    float nm, pn;
+    pcg::ask_constants(bits_per_symbol, &nm, &pn);
+    if (pcg::launch_ask_channel(code, F, n, bits_per_symbol, fading == PCG_FADING_RAYLEIGH, sigma, gain, nm, pn, seed,
+                                out, symbols, reinterpret_cast<hipStream_t>(stream)))
+        return hip_error(hipGetLastError(), "ask_channel launch");
     return PCG_OK;
 }
 

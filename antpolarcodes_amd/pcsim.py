@@ -4,7 +4,7 @@ Restates `Simulation::Simulator` / `SimulationWorker` (src/simulation/simulator.
 david13pod/antPolarCodes) around the batched GPU decoders:
 
   * job list: configureSingleRun / CodeLength / DesignSnr / ListLength / Rate /
-    Amplification / DepthFirstSim / ScanSim (simulator.cpp:126-340), then snrInflateJobList (:361-379), with the
+    Amplification / DepthFirstSim / ScanSim / AskSim (simulator.cpp:126-357), then snrInflateJobList (:361-379), with the
     reference's float32 arithmetic for the SNR / design-SNR / rate / amplification grids;
   * per job (SimulationWorker::run, :632-672): Bhattacharyya frozen set (:680-697),
     encoder + decoder by precision and list size (setCoders :699-760: L > 1 -> Adaptive
@@ -12,7 +12,9 @@ david13pod/antPolarCodes) around the batched GPU decoders:
     fastsscan -> Scan / FastSscanFloat with L as iteration / trial limit, simtype depthfirst ->
     DepthFirst with L as trial limit, all three -p 32 only), CRC-8 / CRC-32 /
     none (setErrorDetector :761-805; "cmac*" is outside this build), BPSK-AWGN at
-    Es/N0 = Eb/N0 * BPS * K / N (setChannel :806-824), Scale(amplification) of the
+    Es/N0 = Eb/N0 * BPS * K / N (setChannel :806-824; simtype ask -> Modulation::Ask at 2 .. 10
+    bits per symbol, configureAskSim :342-357; --channel rayleigh -> Transmission::Rayleigh, which
+    the reference's library has and its simulator never selects), Scale(amplification) of the
     demodulated symbols (:920-937), warm-up min(blocks / 8, 1000) blocks, then the
     counted blocks: BER over the K decoded bits, block errors, reported (check()) errors
     (countErrors :938-965, calculateStatistics :966-985);
@@ -27,7 +29,7 @@ channel noise comes from the device Philox generator, not std::mt19937.
 
 Usage: python -m antpolarcodes_amd.pcsim [simtype] [-w BITS] [--snr-min X] [--snr-max X]
        [--snr-count C] [-n N] [-r RATE] [-l L] [-d DSNR] [-e crc8|crc32|none] [-s]
-       [-p 8|32|832] [-a AMP] [-o NAME] [-t THREADS] [--batch F]
+       [-p 8|32|832] [-a AMP] [-o NAME] [-t THREADS] [--batch F] [--channel awgn|rayleigh]
 """
 import argparse
 import math
@@ -42,7 +44,7 @@ import numpy as np
 SIMTYPES = ("single", "codelength", "designsnr", "listlength", "rate", "amplification", "fixed", "depthfirst",
             "scan", "fastsscan", "ask", "compareall", "getcode")
 SUPPORTED = ("single", "codelength", "designsnr", "listlength", "rate", "amplification", "depthfirst", "scan",
-             "fastsscan", "getcode")
+             "fastsscan", "ask", "getcode")
 CSV_HEADER = ('"N","K","dSNR","C","L","Eb/N0","BPS","BLER","BER","RER","Runs","Errors","Time","Blockspeed",'
               '"Coded Bitrate","Payload Bitrate","Effective Payload Bitrate","Encoder Bitrate","Amplification",'
               '"time min","time max","time mean","time deviation"')
@@ -78,6 +80,7 @@ class Job:
     precision: int
     amplification: float
     bitsPerSymbol: int = 1
+    channel: str = "awgn"  # this build's --channel: "awgn" (Transmission::Awgn) or "rayleigh"
     name: str = ""
     # decoderType: "" = tFlexible (by precision and L), "scan" = tScan, "fastsscan" = tFastSscan,
     # "depthfirst" = tDepthFirst
@@ -111,7 +114,7 @@ def default_job(a):
                errorDetection=error_detection_id(a.error_detection),
                errorDetectionType=error_detection_type(a.error_detection), systematic=not a.non_systematic,
                EbN0=float(f32(a.snr_max)), BlocksToSimulate=int(a.workload) // N, precision=int(a.precision),
-               amplification=float(f32(a.amplification)))
+               amplification=float(f32(a.amplification)), channel=getattr(a, "channel", "awgn"))
 
 
 def _grid(lo, hi, count):
@@ -164,6 +167,9 @@ def configure(a):
             jobs.append(replace(t, L=l, decoder=st))
             l *= 2
         return jobs
+    if st == "ask":
+        # configureAskSim (:342-357): the default job at 2 .. 10 bits per ASK symbol
+        return [replace(t, bitsPerSymbol=b) for b in range(2, 11)]
     raise SystemExit(f"pcsim: simulation type '{st}' is outside this build "
                      f"(supported: {', '.join(SUPPORTED)})")
 
@@ -293,7 +299,10 @@ class GpuBackend:
                 raise SystemExit(f"No decoder present for {job.precision}-bit decoding.")
             self.plan = Plan(job.N, 1, self.frozen, job.systematic, crc, self.device, fixed=job.precision != 32)
         esn0 = 10.0 ** (job.EbN0 / 10.0) * job.bitsPerSymbol * job.K / job.N
-        self.sigma = float(np.sqrt(1.0 / (2.0 * esn0)))
+        if job.channel not in ("awgn", "rayleigh"):
+            raise SystemExit(f"pcsim: channel '{job.channel}' is outside this build (awgn, rayleigh)")
+        # Awgn::setEsN0Linear: 1 / sqrt(2 Es/N0) (awgn.cpp:34); Rayleigh's: 1 / sqrt(Es/N0) (rayleigh.cpp:34)
+        self.sigma = float(np.sqrt(1.0 / (2.0 * esn0))) if job.channel == "awgn" else float(np.sqrt(1.0 / esn0))
         # the device channel returns 2 y / sigma^2; the reference decodes amplification * y
         self.scale = job.amplification * self.sigma * self.sigma / 2.0
 
@@ -304,7 +313,7 @@ class GpuBackend:
 
     def _frames(self, job, F, seed):
         torch = self.torch
-        from ._native import bpsk_awgn_device, random_info_device
+        from ._native import ask_channel_device, bpsk_awgn_device, random_info_device
         kb = (job.K + 7) // 8
         info = torch.empty((F, kb), dtype=torch.uint8, device=self.dev)
         code = torch.empty((F, job.N // 8), dtype=torch.uint8, device=self.dev)
@@ -315,8 +324,13 @@ class GpuBackend:
         e0.record(st)
         self.enc.encode_device(info, code)
         e1.record(st)
-        bpsk_awgn_device(code, job.N, self.sigma, seed ^ 0x9E3779B97F4A7C15, llr)
-        llr.mul_(self.scale)
+        if job.bitsPerSymbol > 1 or job.channel == "rayleigh":
+            # Ask modulate / transmit / demodulate / Scale(amplification) in one launch
+            ask_channel_device(code, job.N, job.bitsPerSymbol, self.sigma, job.amplification,
+                               seed ^ 0x9E3779B97F4A7C15, llr, fading=job.channel)
+        else:
+            bpsk_awgn_device(code, job.N, self.sigma, seed ^ 0x9E3779B97F4A7C15, llr)
+            llr.mul_(self.scale)
         torch.cuda.synchronize(self.dev)
         return llr, info, e0.elapsed_time(e1) * 1e-3
 
@@ -462,6 +476,8 @@ def parser():
     ap.add_argument("--amp-count", type=int, default=6)
     ap.add_argument("-o", "--output", default="simulation")
     ap.add_argument("-t", "--threads", type=int, default=1)
+    ap.add_argument("--channel", default="awgn", choices=("awgn", "rayleigh"),
+                    help="transmission: AWGN, or Rayleigh fading with AWGN (this build)")
     ap.add_argument("--batch", type=int, default=1 << 16, help="frames per GPU launch (this build)")
     return ap
 

@@ -63,6 +63,8 @@
  *   pcg_random_info, pcg_bpsk_awgn_f32 <- the simulator's frame source
  *                        (src/simulation/simulator.cpp:850-937, bpsk.cpp:54-80,
  *                        awgn.cpp:38-43), counter-based and reproducible from a seed
+ *   pcg_ask_constants, pcg_ask_channel_f32 <- Modulation::Ask, Transmission::Awgn / Rayleigh
+ *                        / Scale (ask.cpp:27-101, rayleigh.cpp:76-112), one launch
  *
  *   pcg_plan_set_initial_metric <- the SCL path-metric carry of a reused decoder
  *                        instance (PathList::setFirstPath keeps mMetric[0],
@@ -600,6 +602,33 @@ int pcg_random_info(uint8_t* info, uint64_t F, uint32_t K, uint64_t seed, void* 
  * sigma <= 0: noiseless, llr = +-1.  Noise from Philox4x32-10 keyed by `seed`. */
 int pcg_bpsk_awgn_f32(const uint8_t* code, uint64_t F, uint32_t n, float sigma, uint64_t seed, float* llr,
                       void* stream);
+
+/* ---- ASK modulation, AWGN or Rayleigh fading, soft demodulation, scaling ----------------
+ * (Modulation::Ask, ask.cpp:27-101; Transmission::Awgn / Rayleigh / Scale.)  One launch from
+ * packed code bits (device F x n/8 bytes, MSB-first, n % 8 == 0) to the floats a decoder
+ * reads (device F x n).  A frame has S = ceil(n / bits_per_symbol) symbols; code bits past n
+ * count as 0 and their outputs are not written.  Per symbol:
+ *   x = level * power_normalizer            level: m = 1, s = 0; per bit m *= (bit ? -1 : +1),
+ *                                           s = 2 s + m
+ *   y = x + sigma g                         PCG_FADING_NONE
+ *   y = x sqrtf(g1 g1 + g2 g2) + sigma g    PCG_FADING_RAYLEIGH: the fading is not normalised
+ *                                           (E[h^2] = 2) and not equalised, as in the reference
+ *   a = y * normal_magnitude; per bit k: out = gain * a, a = |a| - 2^(b-1-k)
+ * sigma <= 0: no additive noise (Rayleigh still fades).  g, g1, g2 are standard normals from
+ * Philox4x32-10 keyed by `seed`, a pure function of (seed, frame, symbol index); with
+ * bits_per_symbol = 1 and PCG_FADING_NONE y equals pcg_bpsk_awgn_f32's noisy symbol bit for
+ * bit (that call returns y * 2 / sigma^2).  symbols: device F x S floats receiving y, or NULL.
+ * PCG_E_ARG for bits_per_symbol outside 1 .. 16, an unknown fading, n % 8 != 0 or a NULL code /
+ * out; a no-op for F == 0.  Asynchronous. */
+#define PCG_FADING_NONE 0 /* AWGN */
+#define PCG_FADING_RAYLEIGH 1
+
+/* Ask::setBitsPerSymbol's mNormalMagnitude and mPowerNormalizer (host only, no device). */
+int pcg_ask_constants(uint32_t bits_per_symbol, float* normal_magnitude, float* power_normalizer);
+
+int pcg_ask_channel_f32(const uint8_t* code, uint64_t F, uint32_t n, uint32_t bits_per_symbol, int fading,
+                        float sigma, float gain, uint64_t seed, float* out, float* symbols /* may be NULL */,
+                        void* stream);
 
 #ifdef __cplusplus
 }
