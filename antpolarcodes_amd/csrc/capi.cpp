@@ -8,6 +8,7 @@
 #include "depthfirst.hpp"
 #include "errorlocator.hpp"
 #include "fsscan.hpp"
+#include "lane_frame.hpp"
 #include "scan.hpp"
 
 #include <hip/hip_runtime.h>
@@ -21,6 +22,25 @@
 #include <vector>
 
 struct HostPipe;
+// The lane = codeword kernels (lane_frame.hpp): which of them a plan runs
+enum LaneKind { LANE_NONE, LANE_SCAN, LANE_FSSCAN, LANE_DEPTHFIRST, LANE_ERRLOC };
+struct LaneKindInfo {
+    const char* name, *article; // in error texts
+    const char* creator;        // the entry point that creates such a plan
+    const char* kernel;
+    bool sign_rows;      // its LDS holds the lanes' sign-bit rows (lane_lds_bytes)
+    uint32_t op_words;   // schedule words per op
+    uint64_t (*wave_cap)(uint32_t N, uint32_t slab_floats);
+};
+static const LaneKindInfo lane_kinds[] = {
+    {"", "", "", "", false, 1, nullptr},
+    {"SCAN", "a", "pcg_plan_create_scan", "scan_kernel", true, 1, pcg::scan_wave_cap},
+    {"Fast-SSCAN", "a", "pcg_plan_create_fsscan", "fsscan_kernel", true, pcg::FSS_WORDS, pcg::fsscan_wave_cap},
+    {"SC-Flip", "an", "pcg_plan_create_depthfirst", "depthfirst_kernel", true, pcg::DF_WORDS,
+     pcg::depthfirst_wave_cap},
+    {"error-locator", "an", "pcg_plan_create_errorlocator", "errorlocator_kernel", false, pcg::DF_WORDS,
+     pcg::errorlocator_wave_cap},
+};
 struct pcg_plan {
     pcg::PlanHost host;
     int device = 0;
@@ -91,35 +111,23 @@ struct pcg_plan {
     hipModule_t rtc_mod = nullptr;
     hipFunction_t rtc_fn = nullptr;
     hipFunction_t rtc_fn_i8 = nullptr; // 8-bit plans: the kernel for int8 channel LLRs (rtc_fn: float LLRs)
-    // SCAN plans (pcg_plan_create_scan; scan.hpp): host.ops holds ScanOp words, host.L = 1
-    bool scan = false;
+    // SCAN, Fast-SSCAN, SC-Flip and error-locator plans (pcg_plan_create_scan / _fsscan /
+    // _depthfirst / _errorlocator): host.ops holds the kind's schedule words, host.L = 1
+    LaneKind lane_kind = LANE_NONE;
+    uint32_t lane_slab = 0;       // words of state per codeword
     uint32_t scan_iters = 0;
-    void* d_ext = nullptr;        // pcg_decode_scan_f32_host: extrinsic staging (floats)
-    uint64_t ext_frames = 0;
-    // Fast-SSCAN plans (pcg_plan_create_fsscan; fsscan.hpp): host.ops holds FsscanOp words
-    bool fsscan = false;
     uint32_t fss_trials = 1;      // trial limit
     int fss_forced = 0;           // run exactly fss_trials passes
-    uint32_t fss_slab = 0;        // floats of state per codeword
-    void* d_trials = nullptr;     // pcg_decode_fsscan_f32_host: trial-count staging (bytes)
-    uint64_t trials_frames = 0;
-    // SC-Flip plans (pcg_plan_create_depthfirst; depthfirst.hpp): host.ops holds DepthFirstOp words
-    bool depthfirst = false;
     uint32_t df_trials = 1;       // trial limit
-    uint32_t df_slab = 0;         // words of state per codeword
-    // error-locator plans (pcg_plan_create_errorlocator; errorlocator.hpp): host.ops holds the
-    // SC-Flip schedule; no information bytes, so no decode entry point but pcg_errorlocator_f32
-    bool errloc = false;
-    uint32_t el_slab = 0;         // words of state per codeword
-    // pcg_errorlocator_f32_host staging: llr | desired | u | bits (floats), first | count (words)
-    float* d_el = nullptr;
-    uint64_t el_frames = 0;
+    // their host-pointer entry points: one staging buffer per array of the call (lane_host)
+    struct Stage {
+        void* d = nullptr;
+        uint64_t frames = 0;
+    } lane_stage[6];
+    const LaneKindInfo& lane() const { return lane_kinds[lane_kind]; }
     // SCAN, Fast-SSCAN, SC-Flip or error locator: no rtc, no 8-bit, no puncturing
-    bool soft_plan() const { return scan || fsscan || depthfirst || errloc; }
-    const char* soft_name() const
-    {
-        return errloc ? "error-locator" : depthfirst ? "SC-Flip" : fsscan ? "Fast-SSCAN" : "SCAN";
-    }
+    bool soft_plan() const { return lane_kind != LANE_NONE; }
+    const char* soft_name() const { return lane().name; }
 };
 
 // The host-pointer pipeline of pcg_decode_f32_host / pcg_decode_i8_host: chunks of the
@@ -227,9 +235,8 @@ void free_plan_device(pcg_plan* p)
         (void)hipStreamSynchronize(nullptr);
     }
     (void)hipFree(p->d_soft);
-    (void)hipFree(p->d_ext);
-    (void)hipFree(p->d_trials);
-    (void)hipFree(p->d_el);
+    for (auto& st : p->lane_stage)
+        (void)hipFree(st.d);
     if (p->last_ev)
         (void)hipEventDestroy(p->last_ev);
     p->last_ev = nullptr;
@@ -476,6 +483,81 @@ int mark_done(pcg_plan* p, hipStream_t s)
     p->last_stream = s;
     p->has_last = true;
     return PCG_OK;
+}
+
+// ---- the lane = codeword kernels (SCAN, Fast-SSCAN, SC-Flip, error locator) ----
+
+int not_lane_plan(LaneKind kind)
+{
+    const LaneKindInfo& k = lane_kinds[kind];
+    return fail(PCG_E_ARG, std::string("not ") + k.article + " " + k.name + " plan (" + k.creator + ")");
+}
+
+// The argument checks of their entry points, in this order: the plan, its kind, F == 0 (PCG_OK: the
+// caller returns), the buffers (`bufs`: all that must not be null are not), a host-only plan, and
+// for the device-pointer forms the frame limit.  The error locator checks its mode, its buffers
+// and the frame limit (in both forms) before F == 0.
+int lane_check(const pcg_plan* p, LaneKind kind, uint64_t F, bool bufs, bool device_form, int mode = PCG_EL_CORRECT)
+{
+    if (!p)
+        return fail(PCG_E_ARG, "null plan");
+    if (p->lane_kind != kind)
+        return not_lane_plan(kind);
+    const bool el = kind == LANE_ERRLOC;
+    if (mode != PCG_EL_REFERENCE && mode != PCG_EL_CORRECT && mode != PCG_EL_FIRST)
+        return fail(PCG_E_ARG, "error locator: unknown mode");
+    if (el && !bufs)
+        return fail(PCG_E_ARG, "null llr buffer");
+    if (el && F > 0xFFFFFFFFull)
+        return fail(PCG_E_ARG, "at most 2^32 - 1 frames per call");
+    if (F == 0)
+        return PCG_OK;
+    if (!bufs)
+        return fail(PCG_E_ARG, "null llr/info buffer");
+    if (p->device < 0)
+        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
+    if (device_form && F > 0xFFFFFFFFull)
+        return fail(PCG_E_ARG, "at most 2^32 - 1 frames per call");
+    return PCG_OK;
+}
+
+// the argument block every such kernel takes, from the plan
+pcg::LaneArgs lane_args(const pcg_plan* p, const float* llr, uint64_t F, uint8_t* info, uint8_t* ok)
+{
+    const auto& h = p->host;
+    pcg::LaneArgs c{};
+    c.llr = llr;
+    c.F = F;
+    c.ops = p->d_ops;
+    c.nops = (uint32_t)h.ops.size() / p->lane().op_words;
+    c.N = h.N;
+    c.K = h.K;
+    c.kb = (h.K + 7) / 8;
+    c.info_pos = p->d_info_pos;
+    c.crc_c0 = h.crc_c0;
+    c.crc_bits = (uint32_t)h.crc_kind;
+    c.crc_rows = p->d_crc_m + h.crc_m.size();
+    c.info = info;
+    c.ok = ok;
+    c.slab_floats = p->lane_slab;
+    return c;
+}
+
+// one launch over a.c.F frames on `stream`, ordered after the plan's previous one
+template <typename Args>
+int lane_run(pcg_plan* p, Args& a, int (*launch)(const Args&, hipStream_t), void* stream)
+{
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int rc = order_on(p, s);
+    if (rc != 0)
+        return rc;
+    a.c.units = (uint32_t)pcg::wave_units(a.c.F, 64, p->wave_cap);
+    if ((rc = grow_scratch(p, a.c.units, sizeof(float), s, 64ull * p->lane_slab)) != 0)
+        return rc;
+    a.c.slab = p->d_scratch;
+    if ((rc = launch(a, s)) != 0)
+        return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return mark_done(p, s);
 }
 
 } // namespace
@@ -792,14 +874,8 @@ static int plan_finish(pcg_plan** out, pcg_plan* p, int device)
         return hip_fail(e, "hipMalloc(plan)");
     }
     // wave caps (hipOccupancy) of the lane-serial kernels, once per plan
-    if (p->scan) {
-        p->wave_cap = pcg::scan_wave_cap(h.N, h.systematic);
-    } else if (p->fsscan) {
-        p->wave_cap = pcg::fsscan_wave_cap(h.N, p->fss_slab);
-    } else if (p->depthfirst) {
-        p->wave_cap = pcg::depthfirst_wave_cap(h.N, p->df_slab);
-    } else if (p->errloc) {
-        p->wave_cap = pcg::errorlocator_wave_cap(h.N, p->el_slab);
+    if (p->soft_plan()) {
+        p->wave_cap = p->lane().wave_cap(h.N, p->lane_slab);
     } else if (h.fixed && h.L == 1 && h.sc_kind == 0) {
         p->wave_cap = pcg::sccs_wave_cap(p->wave_lds_floats, false);
         p->wave_cap_i8 = pcg::sccs_wave_cap(p->wave_lds_floats, true);
@@ -946,9 +1022,12 @@ int pcg_plan_describe(const pcg_plan* p, pcg_plan_desc* d)
         return fail(PCG_E_ARG, "null argument");
     d->block_length = p->host.N;
     d->info_length = p->host.K;
-    d->list_size = p->scan ? p->scan_iters : p->fsscan ? p->fss_trials : p->depthfirst ? p->df_trials : p->host.L;
+    d->list_size = p->lane_kind == LANE_SCAN         ? p->scan_iters
+                   : p->lane_kind == LANE_FSSCAN     ? p->fss_trials
+                   : p->lane_kind == LANE_DEPTHFIRST ? p->df_trials
+                                                     : p->host.L;
     d->node_count = p->host.node_count;
-    d->op_count = (uint32_t)p->host.ops.size() / (p->fsscan ? pcg::FSS_WORDS : (p->depthfirst || p->errloc) ? pcg::DF_WORDS : 1u);
+    d->op_count = (uint32_t)p->host.ops.size() / p->lane().op_words;
     d->lds_bytes = p->wave_lds_floats * 4;
     d->scratch_bytes = p->scratch_floats * 4;
     d->crc_kind = p->host.crc_kind;
@@ -1015,111 +1094,37 @@ static int decode_impl(pcg_plan* p,
 static int decode_scan(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info, uint8_t* ok, float* soft, float* ext,
                        void* stream)
 {
-    const auto& h = p->host;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    pcg::ScanArgs a{};
-    a.llr = llr;
-    a.F = F;
-    a.ops = p->d_ops;
-    a.nops = (uint32_t)h.ops.size();
-    a.N = h.N;
-    a.log2N = h.log2N;
-    a.K = h.K;
-    a.kb = (h.K + 7) / 8;
+    pcg::ScanArgs a{lane_args(p, llr, F, info, ok)};
+    a.log2N = p->host.log2N;
     a.iters = p->scan_iters;
-    a.info_pos = p->d_info_pos;
-    a.crc_c0 = h.crc_c0;
-    a.crc_bits = (uint32_t)h.crc_kind;
-    a.crc_rows = p->d_crc_m + h.crc_m.size();
-    a.systematic = h.systematic;
-    a.info = info;
-    a.ok = ok;
+    a.systematic = p->host.systematic;
     a.soft = soft;
     a.ext = ext;
-    int rc = order_on(p, s);
-    if (rc != 0)
-        return rc;
-    a.units = (uint32_t)pcg::wave_units(F, 64, p->wave_cap);
-    if ((rc = grow_scratch(p, a.units, sizeof(float), s, pcg::scan_slab_floats(h.N, h.systematic))) != 0)
-        return rc;
-    a.slab = p->d_scratch;
-    if ((rc = pcg::launch_scan(a, s)) != 0)
-        return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return mark_done(p, s);
+    return lane_run(p, a, pcg::launch_scan, stream);
 }
 
 // FastSscanFloat::decode (fastsscan_float.cpp:309-339) over F frames: one launch of fsscan_kernel
 static int decode_fsscan(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info, uint8_t* ok, float* soft,
                          uint8_t* trials, void* stream)
 {
-    const auto& h = p->host;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    pcg::FsscanArgs a{};
-    a.llr = llr;
-    a.F = F;
-    a.ops = p->d_ops;
-    a.nops = (uint32_t)h.ops.size() / pcg::FSS_WORDS;
-    a.N = h.N;
-    a.K = h.K;
-    a.kb = (h.K + 7) / 8;
+    pcg::FsscanArgs a{lane_args(p, llr, F, info, ok)};
     a.trials = p->fss_trials;
     a.forced = p->fss_forced;
-    a.info_pos = p->d_info_pos;
-    a.crc_c0 = h.crc_c0;
-    a.crc_bits = (uint32_t)h.crc_kind;
-    a.crc_rows = p->d_crc_m + h.crc_m.size();
-    a.info = info;
-    a.ok = ok;
     a.soft = soft;
     a.ntrials = trials;
-    a.slab_floats = p->fss_slab;
-    int rc = order_on(p, s);
-    if (rc != 0)
-        return rc;
-    a.units = (uint32_t)pcg::wave_units(F, 64, p->wave_cap);
-    if ((rc = grow_scratch(p, a.units, sizeof(float), s, 64ull * p->fss_slab)) != 0)
-        return rc;
-    a.slab = p->d_scratch;
-    if ((rc = pcg::launch_fsscan(a, s)) != 0)
-        return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return mark_done(p, s);
+    return lane_run(p, a, pcg::launch_fsscan, stream);
 }
 
 // DepthFirst::decode (depth_first.cpp:599-638) over F frames: one launch of depthfirst_kernel
 static int decode_depthfirst(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info, uint8_t* ok, uint32_t* bits,
                              uint8_t* trials, void* stream)
 {
-    const auto& h = p->host;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    pcg::DepthFirstArgs a{};
-    a.llr = llr;
-    a.F = F;
-    a.ops = p->d_ops;
-    a.nops = (uint32_t)h.ops.size() / pcg::DF_WORDS;
-    a.N = h.N;
-    a.K = h.K;
-    a.kb = (h.K + 7) / 8;
+    pcg::DepthFirstArgs a{lane_args(p, llr, F, info, ok)};
     a.trials = p->df_trials;
-    a.systematic = h.systematic;
-    a.info_pos = p->d_info_pos;
-    a.crc_c0 = h.crc_c0;
-    a.crc_bits = (uint32_t)h.crc_kind;
-    a.crc_rows = p->d_crc_m + h.crc_m.size();
-    a.info = info;
-    a.ok = ok;
+    a.systematic = p->host.systematic;
     a.bits = bits;
     a.ntrials = trials;
-    a.slab_floats = p->df_slab;
-    int rc = order_on(p, s);
-    if (rc != 0)
-        return rc;
-    a.units = (uint32_t)pcg::wave_units(F, 64, p->wave_cap);
-    if ((rc = grow_scratch(p, a.units, sizeof(float), s, 64ull * p->df_slab)) != 0)
-        return rc;
-    a.slab = p->d_scratch;
-    if ((rc = pcg::launch_depthfirst(a, s)) != 0)
-        return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return mark_done(p, s);
+    return lane_run(p, a, pcg::launch_depthfirst, stream);
 }
 
 static int decode_adaptive(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info, uint8_t* ok, float* metrics,
@@ -1163,7 +1168,7 @@ int pcg_decode_f32(pcg_plan* p,
 {
     if (!p)
         return fail(PCG_E_ARG, "null plan");
-    if (p->errloc)
+    if (p->lane_kind == LANE_ERRLOC)
         return fail(PCG_E_UNSUPPORTED, "error-locator plans produce no information bytes (pcg_errorlocator_f32)");
     if (F == 0)
         return PCG_OK;
@@ -1174,11 +1179,11 @@ int pcg_decode_f32(pcg_plan* p,
     if (F > 0xFFFFFFFFull)
         return fail(PCG_E_ARG, "at most 2^32 - 1 frames per call");
     DeviceGuard g(p->device);
-    if (p->scan) // info and ok only; there are no path metrics
+    if (p->lane_kind == LANE_SCAN) // info and ok only; there are no path metrics
         return decode_scan(p, llr, F, info, ok, nullptr, nullptr, stream);
-    if (p->fsscan)
+    if (p->lane_kind == LANE_FSSCAN)
         return decode_fsscan(p, llr, F, info, ok, nullptr, nullptr, stream);
-    if (p->depthfirst)
+    if (p->lane_kind == LANE_DEPTHFIRST)
         return decode_depthfirst(p, llr, F, info, ok, nullptr, nullptr, stream);
     if (p->fast)
         return decode_adaptive(p, llr, F, info, ok, metrics, stream);
@@ -1498,6 +1503,15 @@ static bool host_pinned(const void* ptr)
     return at.type == hipMemoryTypeHost;
 }
 
+// frames per chunk of a host-pointer call: PCG_HOST_CHUNK, else 64 MB of input within [4096, 65536]
+static uint64_t host_chunk(size_t frame_bytes, uint64_t F)
+{
+    uint64_t chunk = (uint64_t)env_int("PCG_HOST_CHUNK", 0);
+    if (chunk == 0)
+        chunk = std::min<uint64_t>(65536, std::max<uint64_t>(4096, (64ull << 20) / frame_bytes));
+    return std::min<uint64_t>(chunk, F);
+}
+
 static int decode_host_serial(pcg_plan* p, const void* llr, size_t elem, uint64_t F, uint8_t* info, uint8_t* ok,
                               float* metrics, uint64_t chunk)
 {
@@ -1538,10 +1552,7 @@ static int decode_host(pcg_plan* p, const void* llr, size_t elem, uint64_t F, ui
     const uint64_t kb = (h.K + 7) / 8;
     const size_t fb = h.N * elem;
     const int mode = env_int("PCG_HOST_PIPE", 2);
-    uint64_t chunk = (uint64_t)env_int("PCG_HOST_CHUNK", 0);
-    if (chunk == 0)
-        chunk = std::min<uint64_t>(65536, std::max<uint64_t>(4096, (64ull << 20) / fb));
-    chunk = std::min<uint64_t>(chunk, F);
+    const uint64_t chunk = host_chunk(fb, F);
     if (mode == 0)
         return decode_host_serial(p, llr, elem, F, info, ok, metrics, chunk);
     const bool direct = host_pinned(llr);
@@ -1702,7 +1713,7 @@ int pcg_decode_f32_host(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info
 {
     if (!p)
         return fail(PCG_E_ARG, "null plan");
-    if (p->errloc)
+    if (p->lane_kind == LANE_ERRLOC)
         return fail(PCG_E_UNSUPPORTED, "error-locator plans produce no information bytes (pcg_errorlocator_f32)");
     if (F == 0)
         return PCG_OK;
@@ -1710,11 +1721,11 @@ int pcg_decode_f32_host(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info
         return fail(PCG_E_ARG, "null llr/info buffer");
     if (p->device < 0)
         return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
-    if (p->scan)
+    if (p->lane_kind == LANE_SCAN)
         return pcg_decode_scan_f32_host(p, llr, F, info, ok, nullptr, nullptr);
-    if (p->fsscan)
+    if (p->lane_kind == LANE_FSSCAN)
         return pcg_decode_fsscan_f32_host(p, llr, F, info, ok, nullptr, nullptr);
-    if (p->depthfirst)
+    if (p->lane_kind == LANE_DEPTHFIRST)
         return pcg_decode_depthfirst_f32_host(p, llr, F, info, ok, nullptr, nullptr);
     DeviceGuard g(p->device);
     return decode_host(p, llr, sizeof(float), F, info, ok, metrics);
@@ -1724,7 +1735,7 @@ static int soft_supported(const pcg_plan* p)
 {
     if (!p)
         return fail(PCG_E_ARG, "null plan");
-    if (p->host.L != 1 || p->host.fixed || p->fast || p->depthfirst || p->errloc)
+    if (p->host.L != 1 || p->host.fixed || p->fast || p->soft_plan())
         return fail(PCG_E_UNSUPPORTED, "soft codewords: Fast-SSC float plans only (FastSscAvxFloat)");
     if (pcg::sc_soft_lds_bytes(p->host.N) == 0)
         return fail(PCG_E_UNSUPPORTED, "soft codewords: block length too large for one wave's LDS");
@@ -1739,12 +1750,12 @@ int pcg_decode_f32_soft(pcg_plan* p,
                         float* soft,
                         void* stream)
 {
-    if (p && p->scan) {
+    if (p && p->lane_kind == LANE_SCAN) {
         if (F != 0 && !soft)
             return fail(PCG_E_ARG, "null llr/info/soft buffer");
         return pcg_decode_scan_f32(p, llr, F, info, ok, soft, nullptr, stream);
     }
-    if (p && p->fsscan) {
+    if (p && p->lane_kind == LANE_FSSCAN) {
         if (F != 0 && !soft)
             return fail(PCG_E_ARG, "null llr/info/soft buffer");
         return pcg_decode_fsscan_f32(p, llr, F, info, ok, soft, nullptr, stream);
@@ -1766,12 +1777,12 @@ int pcg_decode_f32_soft(pcg_plan* p,
 
 int pcg_decode_f32_soft_host(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info, uint8_t* ok, float* soft)
 {
-    if (p && p->scan) {
+    if (p && p->lane_kind == LANE_SCAN) {
         if (F != 0 && !soft)
             return fail(PCG_E_ARG, "null llr/info/soft buffer");
         return pcg_decode_scan_f32_host(p, llr, F, info, ok, soft, nullptr);
     }
-    if (p && p->fsscan) {
+    if (p && p->lane_kind == LANE_FSSCAN) {
         if (F != 0 && !soft)
             return fail(PCG_E_ARG, "null llr/info/soft buffer");
         return pcg_decode_fsscan_f32_host(p, llr, F, info, ok, soft, nullptr);
@@ -1897,6 +1908,90 @@ int pcg_decode_punctured_f32(pcg_plan* p,
     return PCG_OK;
 }
 
+// The common end of pcg_plan_create_{scan,fsscan,depthfirst,errorlocator}: p->host went through
+// the kind's builder (rc, err); the kind's kernel, its LDS and slab sizes, then the device half.
+// Owns p: deleted on failure.
+static int lane_plan_finish(pcg_plan** out, pcg_plan* p, int rc, const std::string& err, LaneKind kind,
+                            uint32_t slab_words, int device)
+{
+    if (rc != 0) {
+        delete p;
+        return fail(rc, err);
+    }
+    p->lane_kind = kind;
+    p->lane_slab = slab_words;
+    p->host.sc_kind = 0;
+    p->rtc_mode = 0;
+    p->kernel = p->lane().kernel;
+    p->wave_lds_floats = pcg::lane_lds_bytes(p->host.N, p->lane().sign_rows) / 4u;
+    p->scratch_floats = slab_words; // per codeword
+    return plan_finish(out, p, device);
+}
+
+// One array of a host-pointer call of such a plan; the i-th of a call is staged in lane_stage[i].
+struct Staged {
+    const void* host; // the caller's array, or null: not asked for
+    bool in;          // copied to the device before each launch, else back after it
+    uint64_t fb;      // bytes per frame
+    const char* what; // names its staging when hipMalloc fails
+};
+
+// The host-pointer form of the lane plans' entry points: chunks of pcg_decode_f32_host's size
+// through staging kept in the plan; the null-stream copies are ordered after the plan's previous
+// decode.  launch(n, d) runs n frames on the null stream, d[i] = the device buffer of arrays[i]
+// (null where the caller's is).
+extern "C++" {
+template <size_t NA, typename Launch>
+static int lane_host(pcg_plan* p, uint64_t F, const Staged (&arrays)[NA], Launch launch)
+{
+    static_assert(NA <= sizeof(p->lane_stage) / sizeof(p->lane_stage[0]), "one staging buffer per array");
+    const uint64_t chunk = host_chunk(p->host.N * sizeof(float), F);
+    int rc = order_on(p, nullptr);
+    if (rc != 0)
+        return rc;
+    hipError_t e;
+    void* d[NA];
+    bool synced = false;
+    for (size_t i = 0; i < NA; ++i) {
+        auto& st = p->lane_stage[i];
+        if (arrays[i].host && st.frames < chunk) {
+            if (!synced && (e = hipStreamSynchronize(nullptr)) != hipSuccess)
+                return hip_fail(e, "hipStreamSynchronize");
+            synced = true;
+            (void)hipFree(st.d);
+            st.d = nullptr;
+            st.frames = 0;
+            if ((e = hipMalloc(&st.d, std::max<uint64_t>(chunk * arrays[i].fb, 1))) != hipSuccess)
+                return hip_fail(e, arrays[i].what);
+            st.frames = chunk;
+        }
+        d[i] = arrays[i].host ? st.d : nullptr;
+    }
+    for (uint64_t f0 = 0; f0 < F; f0 += chunk) {
+        const uint64_t n = std::min(chunk, F - f0);
+        for (size_t i = 0; i < NA; ++i) {
+            const Staged& a = arrays[i];
+            if (a.host && a.in &&
+                (e = hipMemcpy(d[i], static_cast<const char*>(a.host) + f0 * a.fb, n * a.fb, hipMemcpyHostToDevice)) !=
+                    hipSuccess)
+                return hip_fail(e, "hipMemcpy(H2D)");
+        }
+        if ((rc = launch(n, d)) != 0)
+            return rc;
+        for (size_t i = 0; i < NA; ++i) {
+            const Staged& a = arrays[i];
+            if (a.host && !a.in && a.fb &&
+                (e = hipMemcpy(static_cast<char*>(const_cast<void*>(a.host)) + f0 * a.fb, d[i], n * a.fb,
+                               hipMemcpyDeviceToHost)) != hipSuccess)
+                return hip_fail(e, "hipMemcpy(D2H)");
+        }
+        if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) // no output asked for: still synchronous
+            return hip_fail(e, "hipStreamSynchronize");
+    }
+    return PCG_OK;
+}
+} // extern "C++"
+
 int pcg_plan_create_scan(pcg_plan** out,
                          uint32_t N,
                          uint32_t iterations,
@@ -1914,26 +2009,17 @@ int pcg_plan_create_scan(pcg_plan** out,
     auto* p = new pcg_plan();
     std::string err;
     const int rc = pcg::build_scan_plan(p->host, N, frozen, n_frozen, systematic, crc_kind, &err);
-    if (rc != 0) {
-        delete p;
-        return fail(rc, err);
-    }
-    p->scan = true;
     p->scan_iters = iterations;
-    p->host.sc_kind = 0;
-    p->rtc_mode = 0;
-    p->kernel = "scan_kernel";
-    p->wave_lds_floats = pcg::scan_lds_bytes(N) / 4u;
-    p->scratch_floats = pcg::scan_slab_floats(N, p->host.systematic) / 64u; // per codeword
-    return plan_finish(out, p, device);
+    const uint32_t slab = rc == 0 ? (uint32_t)(pcg::scan_slab_floats(N, p->host.systematic) / 64u) : 0u;
+    return lane_plan_finish(out, p, rc, err, LANE_SCAN, slab, device);
 }
 
 int pcg_plan_set_scan_iterations(pcg_plan* p, uint32_t iterations)
 {
     if (!p)
         return fail(PCG_E_ARG, "null plan");
-    if (!p->scan)
-        return fail(PCG_E_ARG, "not a SCAN plan (pcg_plan_create_scan)");
+    if (p->lane_kind != LANE_SCAN)
+        return not_lane_plan(LANE_SCAN);
     if (iterations > 255)
         return fail(PCG_E_ARG, "SCAN: at most 255 iterations");
     p->scan_iters = iterations;
@@ -1949,93 +2035,12 @@ int pcg_decode_scan_f32(pcg_plan* p,
                         float* extrinsic,
                         void* stream)
 {
-    if (!p)
-        return fail(PCG_E_ARG, "null plan");
-    if (!p->scan)
-        return fail(PCG_E_ARG, "not a SCAN plan (pcg_plan_create_scan)");
-    if (F == 0)
-        return PCG_OK;
-    if (!llr || !info)
-        return fail(PCG_E_ARG, "null llr/info buffer");
-    if (p->device < 0)
-        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
-    if (F > 0xFFFFFFFFull)
-        return fail(PCG_E_ARG, "at most 2^32 - 1 frames per call");
+    const int rc = lane_check(p, LANE_SCAN, F, llr && info, true);
+    if (rc != 0 || F == 0)
+        return rc;
     DeviceGuard g(p->device);
     return decode_scan(p, llr, F, info, ok, soft, extrinsic, stream);
 }
-
-// The host-pointer pipeline of the soft-output plans (SCAN, Fast-SSCAN): chunks of
-// pcg_decode_f32_host's size (PCG_HOST_CHUNK overrides it) through staging kept in the plan; the
-// null-stream copies are ordered after the plan's previous decode.  `extra` is the plan's fourth
-// output (extrinsic information / trial counts), xbytes per frame, staged in d_extra (capacity
-// xframes frames); decode(n, d_extra or null) launches n frames from p->d_llr into the staging.
-extern "C++" {
-template <typename Decode>
-static int soft_decode_host(pcg_plan* p, const float* llr, uint64_t F, uint8_t* info, uint8_t* ok, float* soft,
-                            void* extra, uint64_t xbytes, void*& d_extra, uint64_t& xframes, const char* xwhat,
-                            Decode decode)
-{
-    const uint64_t N = p->host.N, kb = (p->host.K + 7) / 8;
-    uint64_t chunk = (uint64_t)env_int("PCG_HOST_CHUNK", 0);
-    if (chunk == 0)
-        chunk = std::min<uint64_t>(65536, std::max<uint64_t>(4096, (64ull << 20) / (N * sizeof(float))));
-    chunk = std::min<uint64_t>(chunk, F);
-    int rc = order_on(p, nullptr);
-    if (rc != 0)
-        return rc;
-    hipError_t e;
-    if (p->stage_frames < chunk || (soft && p->soft_frames < chunk) || (extra && xframes < chunk)) {
-        if ((e = hipStreamSynchronize(nullptr)) != hipSuccess)
-            return hip_fail(e, "hipStreamSynchronize");
-    }
-    if (p->stage_frames < chunk) {
-        (void)hipFree(p->d_llr);
-        (void)hipFree(p->d_info);
-        (void)hipFree(p->d_ok);
-        p->d_llr = nullptr;
-        p->d_info = nullptr;
-        p->d_ok = nullptr;
-        p->stage_frames = 0;
-        if ((e = hipMalloc(&p->d_llr, chunk * N * sizeof(float))) != hipSuccess ||
-            (e = hipMalloc(&p->d_info, chunk * std::max<uint64_t>(kb, 1))) != hipSuccess ||
-            (e = hipMalloc(&p->d_ok, chunk)) != hipSuccess)
-            return hip_fail(e, "hipMalloc(soft-output staging)");
-        p->stage_frames = chunk;
-    }
-    if (soft && p->soft_frames < chunk) {
-        (void)hipFree(p->d_soft);
-        p->d_soft = nullptr;
-        p->soft_frames = 0;
-        if ((e = hipMalloc(&p->d_soft, chunk * N * sizeof(float))) != hipSuccess)
-            return hip_fail(e, "hipMalloc(soft codewords)");
-        p->soft_frames = chunk;
-    }
-    if (extra && xframes < chunk) {
-        (void)hipFree(d_extra);
-        d_extra = nullptr;
-        xframes = 0;
-        if ((e = hipMalloc(&d_extra, chunk * xbytes)) != hipSuccess)
-            return hip_fail(e, xwhat);
-        xframes = chunk;
-    }
-    for (uint64_t f0 = 0; f0 < F; f0 += chunk) {
-        const uint64_t n = std::min(chunk, F - f0);
-        if ((e = hipMemcpy(p->d_llr, llr + f0 * N, n * N * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
-            return hip_fail(e, "hipMemcpy(H2D)");
-        if ((rc = decode(n, extra ? d_extra : nullptr)) != 0)
-            return rc;
-        if ((kb && (e = hipMemcpy(info + f0 * kb, p->d_info, n * kb, hipMemcpyDeviceToHost)) != hipSuccess) ||
-            (ok && (e = hipMemcpy(ok + f0, p->d_ok, n, hipMemcpyDeviceToHost)) != hipSuccess) ||
-            (soft && (e = hipMemcpy(soft + f0 * N, p->d_soft, n * N * sizeof(float), hipMemcpyDeviceToHost)) !=
-                         hipSuccess) ||
-            (extra && (e = hipMemcpy(static_cast<uint8_t*>(extra) + f0 * xbytes, d_extra, n * xbytes,
-                                     hipMemcpyDeviceToHost)) != hipSuccess))
-            return hip_fail(e, "hipMemcpy(D2H)");
-    }
-    return PCG_OK;
-}
-} // extern "C++"
 
 int pcg_decode_scan_f32_host(pcg_plan* p,
                              const float* llr,
@@ -2045,22 +2050,21 @@ int pcg_decode_scan_f32_host(pcg_plan* p,
                              float* soft,
                              float* extrinsic)
 {
-    if (!p)
-        return fail(PCG_E_ARG, "null plan");
-    if (!p->scan)
-        return fail(PCG_E_ARG, "not a SCAN plan (pcg_plan_create_scan)");
-    if (F == 0)
-        return PCG_OK;
-    if (!llr || !info)
-        return fail(PCG_E_ARG, "null llr/info buffer");
-    if (p->device < 0)
-        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
+    const int rc = lane_check(p, LANE_SCAN, F, llr && info, false);
+    if (rc != 0 || F == 0)
+        return rc;
     DeviceGuard g(p->device);
-    return soft_decode_host(p, llr, F, info, ok, soft, extrinsic, p->host.N * sizeof(float), p->d_ext, p->ext_frames,
-                            "hipMalloc(extrinsic information)", [&](uint64_t n, void* d_x) {
-                                return decode_scan(p, p->d_llr, n, p->d_info, ok ? p->d_ok : nullptr,
-                                                   soft ? p->d_soft : nullptr, static_cast<float*>(d_x), nullptr);
-                            });
+    const uint64_t row = p->host.N * sizeof(float), kb = (p->host.K + 7) / 8;
+    const char* what = "hipMalloc(soft-output staging)";
+    const Staged arrays[] = {{llr, true, row, what},
+                             {info, false, kb, what},
+                             {ok, false, 1, what},
+                             {soft, false, row, "hipMalloc(soft codewords)"},
+                             {extrinsic, false, row, "hipMalloc(extrinsic information)"}};
+    return lane_host(p, F, arrays, [&](uint64_t n, void* const* d) {
+        return decode_scan(p, (const float*)d[0], n, (uint8_t*)d[1], (uint8_t*)d[2], (float*)d[3], (float*)d[4],
+                           nullptr);
+    });
 }
 
 int pcg_plan_create_fsscan(pcg_plan** out,
@@ -2079,27 +2083,18 @@ int pcg_plan_create_fsscan(pcg_plan** out,
         return fail(PCG_E_ARG, "Fast-SSCAN: the trial limit must be in [1, 255]");
     auto* p = new pcg_plan();
     std::string err;
-    const int rc = pcg::build_fsscan_plan(p->host, N, frozen, n_frozen, systematic, crc_kind, &p->fss_slab, &err);
-    if (rc != 0) {
-        delete p;
-        return fail(rc, err);
-    }
-    p->fsscan = true;
+    uint32_t slab = 0;
+    const int rc = pcg::build_fsscan_plan(p->host, N, frozen, n_frozen, systematic, crc_kind, &slab, &err);
     p->fss_trials = trial_limit;
-    p->host.sc_kind = 0;
-    p->rtc_mode = 0;
-    p->kernel = "fsscan_kernel";
-    p->wave_lds_floats = pcg::fsscan_lds_bytes(N) / 4u;
-    p->scratch_floats = p->fss_slab; // per codeword
-    return plan_finish(out, p, device);
+    return lane_plan_finish(out, p, rc, err, LANE_FSSCAN, slab, device);
 }
 
 int pcg_plan_set_fsscan_trials(pcg_plan* p, uint32_t trial_limit, int forced)
 {
     if (!p)
         return fail(PCG_E_ARG, "null plan");
-    if (!p->fsscan)
-        return fail(PCG_E_ARG, "not a Fast-SSCAN plan (pcg_plan_create_fsscan)");
+    if (p->lane_kind != LANE_FSSCAN)
+        return not_lane_plan(LANE_FSSCAN);
     if (trial_limit < 1 || trial_limit > 255)
         return fail(PCG_E_ARG, "Fast-SSCAN: the trial limit must be in [1, 255]");
     p->fss_trials = trial_limit;
@@ -2116,18 +2111,9 @@ int pcg_decode_fsscan_f32(pcg_plan* p,
                           uint8_t* trials,
                           void* stream)
 {
-    if (!p)
-        return fail(PCG_E_ARG, "null plan");
-    if (!p->fsscan)
-        return fail(PCG_E_ARG, "not a Fast-SSCAN plan (pcg_plan_create_fsscan)");
-    if (F == 0)
-        return PCG_OK;
-    if (!llr || !info)
-        return fail(PCG_E_ARG, "null llr/info buffer");
-    if (p->device < 0)
-        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
-    if (F > 0xFFFFFFFFull)
-        return fail(PCG_E_ARG, "at most 2^32 - 1 frames per call");
+    const int rc = lane_check(p, LANE_FSSCAN, F, llr && info, true);
+    if (rc != 0 || F == 0)
+        return rc;
     DeviceGuard g(p->device);
     return decode_fsscan(p, llr, F, info, ok, soft, trials, stream);
 }
@@ -2140,22 +2126,21 @@ int pcg_decode_fsscan_f32_host(pcg_plan* p,
                                float* soft,
                                uint8_t* trials)
 {
-    if (!p)
-        return fail(PCG_E_ARG, "null plan");
-    if (!p->fsscan)
-        return fail(PCG_E_ARG, "not a Fast-SSCAN plan (pcg_plan_create_fsscan)");
-    if (F == 0)
-        return PCG_OK;
-    if (!llr || !info)
-        return fail(PCG_E_ARG, "null llr/info buffer");
-    if (p->device < 0)
-        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
+    const int rc = lane_check(p, LANE_FSSCAN, F, llr && info, false);
+    if (rc != 0 || F == 0)
+        return rc;
     DeviceGuard g(p->device);
-    return soft_decode_host(p, llr, F, info, ok, soft, trials, 1, p->d_trials, p->trials_frames,
-                            "hipMalloc(trial counts)", [&](uint64_t n, void* d_x) {
-                                return decode_fsscan(p, p->d_llr, n, p->d_info, ok ? p->d_ok : nullptr,
-                                                     soft ? p->d_soft : nullptr, static_cast<uint8_t*>(d_x), nullptr);
-                            });
+    const uint64_t row = p->host.N * sizeof(float), kb = (p->host.K + 7) / 8;
+    const char* what = "hipMalloc(soft-output staging)";
+    const Staged arrays[] = {{llr, true, row, what},
+                             {info, false, kb, what},
+                             {ok, false, 1, what},
+                             {soft, false, row, "hipMalloc(soft codewords)"},
+                             {trials, false, 1, "hipMalloc(trial counts)"}};
+    return lane_host(p, F, arrays, [&](uint64_t n, void* const* d) {
+        return decode_fsscan(p, (const float*)d[0], n, (uint8_t*)d[1], (uint8_t*)d[2], (float*)d[3], (uint8_t*)d[4],
+                             nullptr);
+    });
 }
 
 int pcg_plan_create_depthfirst(pcg_plan** out,
@@ -2172,28 +2157,19 @@ int pcg_plan_create_depthfirst(pcg_plan** out,
     *out = nullptr;
     auto* p = new pcg_plan();
     std::string err;
-    const int rc = pcg::build_depthfirst_plan(p->host, N, trial_limit, frozen, n_frozen, systematic, crc_kind,
-                                              &p->df_slab, &err);
-    if (rc != 0) {
-        delete p;
-        return fail(rc, err);
-    }
-    p->depthfirst = true;
+    uint32_t slab = 0;
+    const int rc =
+        pcg::build_depthfirst_plan(p->host, N, trial_limit, frozen, n_frozen, systematic, crc_kind, &slab, &err);
     p->df_trials = trial_limit;
-    p->host.sc_kind = 0;
-    p->rtc_mode = 0;
-    p->kernel = "depthfirst_kernel";
-    p->wave_lds_floats = pcg::depthfirst_lds_bytes(N) / 4u;
-    p->scratch_floats = p->df_slab; // per codeword
-    return plan_finish(out, p, device);
+    return lane_plan_finish(out, p, rc, err, LANE_DEPTHFIRST, slab, device);
 }
 
 int pcg_plan_set_depthfirst_trials(pcg_plan* p, uint32_t trial_limit)
 {
     if (!p)
         return fail(PCG_E_ARG, "null plan");
-    if (!p->depthfirst)
-        return fail(PCG_E_ARG, "not an SC-Flip plan (pcg_plan_create_depthfirst)");
+    if (p->lane_kind != LANE_DEPTHFIRST)
+        return not_lane_plan(LANE_DEPTHFIRST);
     if (trial_limit < 1 || trial_limit > pcg::DF_MAX_TRIALS)
         return fail(PCG_E_ARG, "SC-Flip: the trial limit must be in [1, 255]");
     if (p->host.K < std::max<uint32_t>(trial_limit, 2))
@@ -2211,18 +2187,9 @@ int pcg_decode_depthfirst_f32(pcg_plan* p,
                               uint8_t* trials,
                               void* stream)
 {
-    if (!p)
-        return fail(PCG_E_ARG, "null plan");
-    if (!p->depthfirst)
-        return fail(PCG_E_ARG, "not an SC-Flip plan (pcg_plan_create_depthfirst)");
-    if (F == 0)
-        return PCG_OK;
-    if (!llr || !info)
-        return fail(PCG_E_ARG, "null llr/info buffer");
-    if (p->device < 0)
-        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
-    if (F > 0xFFFFFFFFull)
-        return fail(PCG_E_ARG, "at most 2^32 - 1 frames per call");
+    const int rc = lane_check(p, LANE_DEPTHFIRST, F, llr && info, true);
+    if (rc != 0 || F == 0)
+        return rc;
     DeviceGuard g(p->device);
     return decode_depthfirst(p, llr, F, info, ok, bits, trials, stream);
 }
@@ -2235,24 +2202,21 @@ int pcg_decode_depthfirst_f32_host(pcg_plan* p,
                                    uint32_t* bits,
                                    uint8_t* trials)
 {
-    if (!p)
-        return fail(PCG_E_ARG, "null plan");
-    if (!p->depthfirst)
-        return fail(PCG_E_ARG, "not an SC-Flip plan (pcg_plan_create_depthfirst)");
-    if (F == 0)
-        return PCG_OK;
-    if (!llr || !info)
-        return fail(PCG_E_ARG, "null llr/info buffer");
-    if (p->device < 0)
-        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
+    const int rc = lane_check(p, LANE_DEPTHFIRST, F, llr && info, false);
+    if (rc != 0 || F == 0)
+        return rc;
     DeviceGuard g(p->device);
-    // the decoded words travel through the chunking helper's soft-codeword staging (N words a frame)
-    return soft_decode_host(p, llr, F, info, ok, reinterpret_cast<float*>(bits), trials, 1, p->d_trials,
-                            p->trials_frames, "hipMalloc(trial counts)", [&](uint64_t n, void* d_x) {
-                                return decode_depthfirst(p, p->d_llr, n, p->d_info, ok ? p->d_ok : nullptr,
-                                                         bits ? reinterpret_cast<uint32_t*>(p->d_soft) : nullptr,
-                                                         static_cast<uint8_t*>(d_x), nullptr);
-                            });
+    const uint64_t row = p->host.N * sizeof(float), kb = (p->host.K + 7) / 8;
+    const char* what = "hipMalloc(soft-output staging)";
+    const Staged arrays[] = {{llr, true, row, what},
+                             {info, false, kb, what},
+                             {ok, false, 1, what},
+                             {bits, false, row, "hipMalloc(decoded words)"},
+                             {trials, false, 1, "hipMalloc(trial counts)"}};
+    return lane_host(p, F, arrays, [&](uint64_t n, void* const* d) {
+        return decode_depthfirst(p, (const float*)d[0], n, (uint8_t*)d[1], (uint8_t*)d[2], (uint32_t*)d[3],
+                                 (uint8_t*)d[4], nullptr);
+    });
 }
 
 int pcg_plan_create_errorlocator(pcg_plan** out, uint32_t N, const uint32_t* frozen, uint32_t n_frozen, int device)
@@ -2262,18 +2226,9 @@ int pcg_plan_create_errorlocator(pcg_plan** out, uint32_t N, const uint32_t* fro
     *out = nullptr;
     auto* p = new pcg_plan();
     std::string err;
-    const int rc = pcg::build_errorlocator_plan(p->host, N, frozen, n_frozen, &p->el_slab, &err);
-    if (rc != 0) {
-        delete p;
-        return fail(rc, err);
-    }
-    p->errloc = true;
-    p->host.sc_kind = 0;
-    p->rtc_mode = 0;
-    p->kernel = "errorlocator_kernel";
-    p->wave_lds_floats = pcg::errorlocator_lds_bytes(N) / 4u;
-    p->scratch_floats = p->el_slab; // per codeword
-    return plan_finish(out, p, device);
+    uint32_t slab = 0;
+    const int rc = pcg::build_errorlocator_plan(p->host, N, frozen, n_frozen, &slab, &err);
+    return lane_plan_finish(out, p, rc, err, LANE_ERRLOC, slab, device);
 }
 
 // ErrorLocator::decode / decodeFindFirstError (errorlocator.cpp:214-232) over F frames: one launch
@@ -2281,46 +2236,14 @@ int pcg_plan_create_errorlocator(pcg_plan** out, uint32_t N, const uint32_t* fro
 static int run_errorlocator(pcg_plan* p, int mode, const float* llr, const float* desired, uint64_t F, float* u,
                             uint32_t* bits, int32_t* first, uint32_t* count, void* stream)
 {
-    const auto& h = p->host;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    pcg::ErrorLocatorArgs a{};
-    a.llr = llr;
+    pcg::ErrorLocatorArgs a{lane_args(p, llr, F, nullptr, nullptr)};
     a.desired = desired;
-    a.F = F;
-    a.ops = p->d_ops;
-    a.nops = (uint32_t)h.ops.size() / pcg::DF_WORDS;
-    a.N = h.N;
     a.mode = (uint32_t)mode;
     a.u = u;
     a.bits = bits;
     a.first = first;
     a.count = count;
-    a.slab_floats = p->el_slab;
-    int rc = order_on(p, s);
-    if (rc != 0)
-        return rc;
-    a.units = (uint32_t)pcg::wave_units(F, 64, p->wave_cap);
-    if ((rc = grow_scratch(p, a.units, sizeof(float), s, 64ull * p->el_slab)) != 0)
-        return rc;
-    a.slab = p->d_scratch;
-    if ((rc = pcg::launch_errorlocator(a, s)) != 0)
-        return fail(rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return mark_done(p, s);
-}
-
-static int errorlocator_args(const pcg_plan* p, int mode, const float* llr, uint64_t F)
-{
-    if (!p)
-        return fail(PCG_E_ARG, "null plan");
-    if (!p->errloc)
-        return fail(PCG_E_ARG, "not an error-locator plan (pcg_plan_create_errorlocator)");
-    if (mode != PCG_EL_REFERENCE && mode != PCG_EL_CORRECT && mode != PCG_EL_FIRST)
-        return fail(PCG_E_ARG, "error locator: unknown mode");
-    if (!llr)
-        return fail(PCG_E_ARG, "null llr buffer");
-    if (F > 0xFFFFFFFFull)
-        return fail(PCG_E_ARG, "at most 2^32 - 1 frames per call");
-    return PCG_OK;
+    return lane_run(p, a, pcg::launch_errorlocator, stream);
 }
 
 int pcg_errorlocator_f32(pcg_plan* p,
@@ -2334,13 +2257,9 @@ int pcg_errorlocator_f32(pcg_plan* p,
                          uint32_t* count,
                          void* stream)
 {
-    const int rc = errorlocator_args(p, mode, llr, F);
-    if (rc != 0)
+    const int rc = lane_check(p, LANE_ERRLOC, F, llr != nullptr, true, mode);
+    if (rc != 0 || F == 0)
         return rc;
-    if (F == 0)
-        return PCG_OK;
-    if (p->device < 0)
-        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
     DeviceGuard g(p->device);
     return run_errorlocator(p, mode, llr, desired, F, u, bits, first, count, stream);
 }
@@ -2355,58 +2274,18 @@ int pcg_errorlocator_f32_host(pcg_plan* p,
                               int32_t* first,
                               uint32_t* count)
 {
-    int rc = errorlocator_args(p, mode, llr, F);
-    if (rc != 0)
+    const int rc = lane_check(p, LANE_ERRLOC, F, llr != nullptr, false, mode);
+    if (rc != 0 || F == 0)
         return rc;
-    if (F == 0)
-        return PCG_OK;
-    if (p->device < 0)
-        return fail(PCG_E_NODEVICE, "host-only plan (created with device < 0)");
     DeviceGuard g(p->device);
-    // chunks of pcg_decode_f32_host's size through staging kept in the plan (4 N + 2 words a frame)
-    const uint64_t N = p->host.N;
-    uint64_t chunk = (uint64_t)env_int("PCG_HOST_CHUNK", 0);
-    if (chunk == 0)
-        chunk = std::min<uint64_t>(65536, std::max<uint64_t>(4096, (64ull << 20) / (N * sizeof(float))));
-    chunk = std::min<uint64_t>(chunk, F);
-    if ((rc = order_on(p, nullptr)) != 0)
-        return rc;
-    hipError_t e;
-    if (p->el_frames < chunk) {
-        if ((e = hipStreamSynchronize(nullptr)) != hipSuccess)
-            return hip_fail(e, "hipStreamSynchronize");
-        (void)hipFree(p->d_el);
-        p->d_el = nullptr;
-        p->el_frames = 0;
-        if ((e = hipMalloc(&p->d_el, chunk * (4 * N + 2) * sizeof(float))) != hipSuccess)
-            return hip_fail(e, "hipMalloc(error-locator staging)");
-        p->el_frames = chunk;
-    }
-    float* d_llr = p->d_el;
-    float* d_des = d_llr + chunk * N;
-    float* d_u = d_des + chunk * N;
-    uint32_t* d_bits = reinterpret_cast<uint32_t*>(d_u + chunk * N);
-    int32_t* d_first = reinterpret_cast<int32_t*>(d_bits + chunk * N);
-    uint32_t* d_count = reinterpret_cast<uint32_t*>(d_first + chunk);
-    for (uint64_t f0 = 0; f0 < F; f0 += chunk) {
-        const uint64_t n = std::min(chunk, F - f0);
-        if ((e = hipMemcpy(d_llr, llr + f0 * N, n * N * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess ||
-            (desired &&
-             (e = hipMemcpy(d_des, desired + f0 * N, n * N * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess))
-            return hip_fail(e, "hipMemcpy(H2D)");
-        if ((rc = run_errorlocator(p, mode, d_llr, desired ? d_des : nullptr, n, u ? d_u : nullptr,
-                                   bits ? d_bits : nullptr, first ? d_first : nullptr, count ? d_count : nullptr,
-                                   nullptr)) != 0)
-            return rc;
-        if ((u && (e = hipMemcpy(u + f0 * N, d_u, n * N * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) ||
-            (bits && (e = hipMemcpy(bits + f0 * N, d_bits, n * N * 4, hipMemcpyDeviceToHost)) != hipSuccess) ||
-            (first && (e = hipMemcpy(first + f0, d_first, n * 4, hipMemcpyDeviceToHost)) != hipSuccess) ||
-            (count && (e = hipMemcpy(count + f0, d_count, n * 4, hipMemcpyDeviceToHost)) != hipSuccess))
-            return hip_fail(e, "hipMemcpy(D2H)");
-        if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) // no output asked for: still synchronous
-            return hip_fail(e, "hipStreamSynchronize");
-    }
-    return PCG_OK;
+    const uint64_t row = p->host.N * sizeof(float);
+    const char* what = "hipMalloc(error-locator staging)";
+    const Staged arrays[] = {{llr, true, row, what},  {desired, true, row, what}, {u, false, row, what},
+                             {bits, false, row, what}, {first, false, 4, what},    {count, false, 4, what}};
+    return lane_host(p, F, arrays, [&](uint64_t n, void* const* d) {
+        return run_errorlocator(p, mode, (const float*)d[0], (const float*)d[1], n, (float*)d[2], (uint32_t*)d[3],
+                                (int32_t*)d[4], (uint32_t*)d[5], nullptr);
+    });
 }
 
 void pcg_plan_destroy(pcg_plan* p)

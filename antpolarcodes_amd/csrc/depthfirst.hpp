@@ -34,24 +34,11 @@ constexpr inline uint32_t df_slab_floats(uint32_t N, uint32_t K) { return df_ent
 constexpr uint32_t DF_E_OPT0 = 1u << 24, DF_E_OPT1 = 1u << 25, DF_E_DEPTH1 = 1u << 26, DF_E_DEEPER = 1u << 27;
 
 struct DepthFirstArgs {
-    const float* llr; // F x N channel LLRs (device)
-    uint64_t F;
-    const uint32_t* ops; // flattened schedule of one root decode (device), DF_WORDS words per op
-    uint32_t nops;
-    uint32_t N, K, kb;
-    uint32_t trials; // trial limit, 1 .. 255
+    LaneArgs c;       // ops: the schedule of one root decode, DF_WORDS words per op
+    uint32_t trials;  // trial limit, 1 .. 255
     int systematic;
-    const uint16_t* info_pos;
-    uint32_t crc_c0;
-    uint32_t crc_bits;
-    const uint32_t* crc_rows; // as KernelArgs::crc_rows
-    uint8_t* info;        // F x kb
-    uint8_t* ok;          // F or null
-    uint32_t* bits;       // F x N decoded words or null
-    uint8_t* ntrials;     // F or null: trials run
-    float* slab;          // units x 64 x slab_floats
-    uint32_t slab_floats; // words per lane (a multiple of 4)
-    uint32_t units;       // grid size (persistent waves)
+    uint32_t* bits;   // F x N decoded words or null
+    uint8_t* ntrials; // F or null: trials run
 };
 
 // The SC-Flip plan: validation, info positions and detector model as build_plan; `ops` =
@@ -60,7 +47,6 @@ struct DepthFirstArgs {
 int build_depthfirst_plan(PlanHost& p, uint32_t N, uint32_t trial_limit, const uint32_t* frozen, uint32_t nf,
                           int systematic, int crc_kind, uint32_t* slab_floats, std::string* err);
 
-uint32_t depthfirst_lds_bytes(uint32_t N);
 uint64_t depthfirst_wave_cap(uint32_t N, uint32_t slab_floats);
 int launch_depthfirst(const DepthFirstArgs& a, hipStream_t stream);
 

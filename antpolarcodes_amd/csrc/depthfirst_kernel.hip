@@ -22,14 +22,15 @@
 //
 // A wave runs until all of its lanes have passed their check or used their trials.  A lane that
 // has passed keeps computing with the wave; its outputs are stored once, in its last trial.
+//
+// Frame rows in and out through the transpose tile, the slab access, the detector syndrome, the
+// information bytes and the launch are lane_frame.hpp's (through depthfirst_ops.hpp).
 #include "depthfirst_ops.hpp"
 
 namespace pcg {
 
 namespace {
 
-constexpr uint32_t TILE = 64;        // positions per transpose tile
-constexpr uint32_t TILE_STRIDE = 65; // LDS row stride of a tile (conflict-free columns)
 constexpr uint32_t NO_LEAF = 0xffffu;
 
 // what a lane carries through the leaves of one root decode
@@ -84,7 +85,7 @@ PCG_DEV void leaf8_op(float* sf, uint32_t N, uint32_t l, uint32_t group, uint32_
                       float* rel)
 {
     const uint32_t in = df_lvl(N, l), bp = df_bits(N) + group * 8u;
-    const V4 u = ld4(sf, in), v = ld4(sf, in + 4);
+    const Vec<4> u = ldv<4>(sf, in), v = ldv<4>(sf, in + 4);
     float x[8];
     uint32_t out[8];
 #pragma unroll
@@ -93,14 +94,14 @@ PCG_DEV void leaf8_op(float* sf, uint32_t N, uint32_t l, uint32_t group, uint32_
         x[4 + k] = v.v[k];
     }
     sc_small<8, 0>(x, out, mask, rank0, c, rel);
-    V4 r0, r1;
+    Vec<4> r0, r1;
 #pragma unroll
     for (uint32_t k = 0; k < 4; ++k) {
         r0.v[k] = ubits(out[k]);
         r1.v[k] = ubits(out[4 + k]);
     }
-    st4(sf, bp, r0);
-    st4(sf, bp + 4, r1);
+    stv<4>(sf, bp, r0);
+    stv<4>(sf, bp + 4, r1);
 }
 
 // the leaf after `pv, pi` in (reliability, rank) order among the K first-pass reliabilities
@@ -109,7 +110,7 @@ PCG_DEV void next_weakest(const float* rel, uint32_t K, float pv, uint32_t pi, f
     float bv = __builtin_inff();
     uint32_t bi = NO_LEAF;
     for (uint32_t r = 0; r < K; r += 4) {
-        const V4 q = ld4(rel, r);
+        const Vec<4> q = ldv<4>(rel, r);
 #pragma unroll
         for (uint32_t k = 0; k < 4; ++k) {
             const float m = q.v[k];
@@ -129,52 +130,27 @@ PCG_DEV uint32_t entry0(uint32_t n0, uint32_t opt) { return n0 | (0xfffu << 12) 
 __global__ void __launch_bounds__(64) depthfirst_kernel(DepthFirstArgs a)
 {
     extern __shared__ uint32_t smem_df[];
-    float* tile = reinterpret_cast<float*>(smem_df);
+    uint32_t* tile = smem_df;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t N = a.N, K = a.K, TL = a.trials;
+    const uint32_t N = a.c.N, K = a.c.K, TL = a.trials;
     const uint32_t T = N < TILE ? N : TILE;
     const uint32_t W = N >= 32 ? N / 32 : 1u;
     uint32_t* row = smem_df + TILE * TILE_STRIDE + lane; // own sign-bit row, word q at [q * 64]
-    float* sf = a.slab + (uint64_t)blockIdx.x * a.slab_floats * 64u + lane * 4u;
+    float* sf = a.c.slab + (uint64_t)blockIdx.x * a.c.slab_floats * 64u + lane * 4u;
     float* rel = sf + (uint64_t)df_rel(N) * 64u;
     float* ent = sf + (uint64_t)df_ent(N, K) * 64u;
     const uint32_t BITS = df_bits(N);
     const double log9 = 2.1972245773362196; // log(9): the reference compares in double
-    const uint64_t ngroups = (a.F + 63) / 64;
-    const bool aligned = (reinterpret_cast<uintptr_t>(a.llr) & 15u) == 0; // rows are N * 4 bytes, N >= 8
+    const uint64_t ngroups = (a.c.F + 63) / 64;
+    const bool aligned = (reinterpret_cast<uintptr_t>(a.c.llr) & 15u) == 0; // rows are N * 4 bytes, N >= 8
     for (uint64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
         const uint64_t frame0 = grp * 64, frame = frame0 + lane;
-        const uint32_t nfr = a.F - frame0 < 64 ? (uint32_t)(a.F - frame0) : 64u;
-        // channel LLRs into level 0 (as fsscan_kernel): own rows when 16-byte aligned, else the tile
-        if (aligned) {
-            const float4* src = reinterpret_cast<const float4*>(a.llr + (lane < nfr ? frame : frame0) * N);
-            for (uint32_t e = 0; e < N; e += 32) {
-                float4 v[8];
-#pragma unroll
-                for (uint32_t q = 0; q < 8; ++q)
-                    if (e + 4 * q < N)
-                        v[q] = src[(e >> 2) + q];
-#pragma unroll
-                for (uint32_t q = 0; q < 8; ++q)
-                    if (e + 4 * q < N)
-                        *reinterpret_cast<float4*>(sf + (uint64_t)(e + 4 * q) * 64u) =
-                            lane < nfr ? v[q] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            }
-        }
-        for (uint32_t c = 0; !aligned && c < N / T; ++c) {
-            for (uint32_t f = 0; f < 64; ++f)
-                if (lane < T)
-                    tile[f * TILE_STRIDE + lane] = f < nfr ? a.llr[(frame0 + f) * N + c * T + lane] : 0.0f;
-            wsync();
-            for (uint32_t j = 0; j < T; j += 4) {
-                V4 v;
-#pragma unroll
-                for (uint32_t k = 0; k < 4; ++k)
-                    v.v[k] = tile[lane * TILE_STRIDE + j + k];
-                st4(sf, c * T + j, v);
-            }
-            wsync();
-        }
+        const uint32_t nfr = a.c.F - frame0 < 64 ? (uint32_t)(a.c.F - frame0) : 64u;
+        // channel LLRs into level 0: own rows when 16-byte aligned, else through the tile
+        if (aligned)
+            rows_in_own(sf, 0, a.c.llr, frame0, nfr, N, lane);
+        else
+            rows_in(tile, sf, 0, a.c.llr, frame0, nfr, N, T, lane);
         bool done = lane >= nfr; // passed its check in an earlier trial (or no frame)
         LeafState ls;
         ls.f0 = ls.f1 = ls.excl = NO_LEAF;
@@ -184,8 +160,8 @@ __global__ void __launch_bounds__(64) depthfirst_kernel(DepthFirstArgs a)
             ls.best = __builtin_inff();
             ls.besti = NO_LEAF;
             float* relw = run == 1 && TL > 1 ? rel : nullptr;
-            for (uint32_t k = 0; k < a.nops; ++k) {
-                const uint32_t op = ld_const(a.ops, DF_WORDS * k), w1 = ld_const(a.ops, DF_WORDS * k + 1);
+            for (uint32_t k = 0; k < a.c.nops; ++k) {
+                const uint32_t op = ld_const(a.c.ops, DF_WORDS * k), w1 = ld_const(a.c.ops, DF_WORDS * k + 1);
                 const uint32_t code = scan_code(op), l = scan_level(op), g = scan_group(op);
                 if (code == DF_F)
                     rater_op<DF_F>(sf, N, l, g);
@@ -200,7 +176,7 @@ __global__ void __launch_bounds__(64) depthfirst_kernel(DepthFirstArgs a)
             for (uint32_t q = 0; q < W; ++q) {
                 uint32_t bits = 0;
                 for (uint32_t j = 0; j < 32 && j < N; j += 4) {
-                    const V4 x = ld4(sf, BITS + 32 * q + j);
+                    const Vec<4> x = ldv<4>(sf, BITS + 32 * q + j);
 #pragma unroll
                     for (uint32_t k = 0; k < 4; ++k)
                         bits |= (fbits(x.v[k]) >> 31) << (j + k);
@@ -215,54 +191,18 @@ __global__ void __launch_bounds__(64) depthfirst_kernel(DepthFirstArgs a)
                         if (!(q & d))
                             row[q << 6] ^= row[(q + d) << 6];
             }
-            uint32_t syn = a.crc_c0;
-            for (uint32_t rb = 0; rb < a.crc_bits; ++rb) {
-                uint32_t pc = 0;
-                for (uint32_t q = 0; q < W; ++q)
-                    pc += __builtin_popcount(row[q << 6] & a.crc_rows[rb * W + q]);
-                syn ^= (pc & 1u) << rb;
-            }
-            const bool pass_ok = syn == 0;
+            const bool pass_ok = detector_syndrome(row, W, a.c.crc_c0, a.c.crc_bits, a.c.crc_rows) == 0;
             const bool fin = !done && (pass_ok || run == TL); // this lane's last trial
             if (fin) {
-                uint8_t* out = a.info + frame * a.kb;
-                uint32_t cw = 0xffffffffu, word = 0;
-                for (uint32_t b = 0; b < a.kb; ++b) {
-                    uint32_t byte = 0;
-                    for (uint32_t q = 0; q < 8; ++q) {
-                        const uint32_t idx = 8 * b + q;
-                        if (idx < K) {
-                            const uint32_t pos = a.info_pos[idx];
-                            if ((pos >> 5) != cw) {
-                                cw = pos >> 5;
-                                word = row[cw << 6];
-                            }
-                            byte |= ((word >> (pos & 31u)) & 1u) << (7 - q);
-                        }
-                    }
-                    out[b] = (uint8_t)byte;
-                }
-                if (a.ok)
-                    a.ok[frame] = pass_ok ? 1 : 0;
+                store_info_bytes(row, a.c.info_pos, K, a.c.kb, a.c.info + frame * a.c.kb);
+                if (a.c.ok)
+                    a.c.ok[frame] = pass_ok ? 1 : 0;
                 if (a.ntrials)
                     a.ntrials[frame] = (uint8_t)run;
             }
             const uint64_t finm = ballot(fin);
-            if (a.bits && finm) { // the decoded words of the lanes that finish here, through the tile
-                for (uint32_t c = 0; c < N / T; ++c) {
-                    for (uint32_t j = 0; j < T; j += 4) {
-                        const V4 x = ld4(sf, BITS + c * T + j);
-#pragma unroll
-                        for (uint32_t k = 0; k < 4; ++k)
-                            tile[lane * TILE_STRIDE + j + k] = x.v[k];
-                    }
-                    wsync();
-                    for (uint32_t f = 0; f < nfr; ++f)
-                        if (((finm >> f) & 1u) && lane < T)
-                            a.bits[(frame0 + f) * N + c * T + lane] = fbits(tile[f * TILE_STRIDE + lane]);
-                    wsync();
-                }
-            }
+            if (a.bits && finm) // the decoded words of the lanes that finish here
+                rows_out(tile, sf, BITS, a.bits, frame0, nfr, N, T, lane, finm);
             done = done || pass_ok;
             if (run == TL || ballot(!done) == 0)
                 break;
@@ -328,34 +268,14 @@ __global__ void __launch_bounds__(64) depthfirst_kernel(DepthFirstArgs a)
 
 } // namespace
 
-uint32_t depthfirst_lds_bytes(uint32_t N) { return 4u * (TILE * TILE_STRIDE + 64u * (N >= 32 ? N / 32 : 1u)); }
-
-// Persistent waves of a launch: up to 4 per CU (one per SIMD) as far as they are resident, and
-// as many as keep the slab within 2 GiB.
 uint64_t depthfirst_wave_cap(uint32_t N, uint32_t slab_floats)
 {
-    int dev = 0, cus = 256, res = 0;
-    if (hipGetDevice(&dev) == hipSuccess)
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&res, depthfirst_kernel, 64, depthfirst_lds_bytes(N)) !=
-        hipSuccess)
-        res = 0;
-    uint64_t wpc = res > 0 ? (uint64_t)res : 1;
-    if (wpc > 4)
-        wpc = 4;
-    uint64_t cap = (uint64_t)cus * wpc;
-    const uint64_t fit = (2ull << 30) / (256ull * slab_floats);
-    if (cap > fit)
-        cap = fit ? fit : 1;
-    return cap;
+    return lane_wave_cap(depthfirst_kernel, lane_lds_bytes(N, true), 256ull * slab_floats);
 }
 
 int launch_depthfirst(const DepthFirstArgs& a, hipStream_t stream)
 {
-    if (a.units == 0)
-        return a.F ? -4 : 0;
-    hipLaunchKernelGGL(depthfirst_kernel, dim3(a.units), dim3(64), (size_t)depthfirst_lds_bytes(a.N), stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return lane_launch(depthfirst_kernel, a, lane_lds_bytes(a.c.N, true), stream);
 }
 
 } // namespace pcg

@@ -1,55 +1,39 @@
 // depthfirst_ops.hpp -- device code shared by the kernels that walk plan.cpp's depthfirst_emit
-// schedule with lane = codeword (depthfirst_kernel.hip, errorlocator_kernel.hip): access to a
-// lane's slab of float4 units and the F / G / combine ops of the nodes above size 8.
+// schedule with lane = codeword (depthfirst_kernel.hip, errorlocator_kernel.hip): the F / G /
+// combine ops of the nodes above size 8.  The access to a lane's slab of float4 units and the frame
+// I/O come with lane_frame.hpp.
 #pragma once
 #include "depthfirst.hpp"
-#include "wave.hpp"
+#include "lane_frame.hpp"
 
 namespace pcg {
 
 namespace {
-
-struct V4 {
-    float v[4];
-};
-PCG_DEV V4 ld4(const float* sf, uint32_t off)
-{
-    const float4 t = *reinterpret_cast<const float4*>(sf + (uint64_t)off * 64u);
-    V4 r;
-    r.v[0] = t.x, r.v[1] = t.y, r.v[2] = t.z, r.v[3] = t.w;
-    return r;
-}
-PCG_DEV void st4(float* sf, uint32_t off, const V4& r)
-{
-    *reinterpret_cast<float4*>(sf + (uint64_t)off * 64u) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-}
-// word i of the lane's slab (any i)
-PCG_DEV float* wordp(float* sf, uint32_t i) { return sf + (uint64_t)(i >> 2) * 256u + (i & 3u); }
 
 // F / G / combine of a node over the values [i0, i0 + 4B) of its halves: inputs (a | b) at `in`,
 // the child's input at `nx`, the node's words at `bp`
 template <uint32_t CODE, uint32_t B>
 PCG_DEV void rater_chunk(float* sf, uint32_t in, uint32_t h, uint32_t nx, uint32_t bp, uint32_t i0)
 {
-    V4 a[B], b[B], s[B];
+    Vec<4> a[B], b[B], s[B];
 #pragma unroll
     for (uint32_t q = 0; q < B; ++q) {
         const uint32_t i = i0 + 4 * q;
         if (CODE != DF_COMB) {
-            a[q] = ld4(sf, in + i);
-            b[q] = ld4(sf, in + h + i);
+            a[q] = ldv<4>(sf, in + i);
+            b[q] = ldv<4>(sf, in + h + i);
         }
         if (CODE == DF_G)
-            s[q] = ld4(sf, bp + i);
+            s[q] = ldv<4>(sf, bp + i);
         if (CODE == DF_COMB) {
-            a[q] = ld4(sf, bp + i);
-            b[q] = ld4(sf, bp + h + i);
+            a[q] = ldv<4>(sf, bp + i);
+            b[q] = ldv<4>(sf, bp + h + i);
         }
     }
 #pragma unroll
     for (uint32_t q = 0; q < B; ++q) {
         const uint32_t i = i0 + 4 * q;
-        V4 r;
+        Vec<4> r;
 #pragma unroll
         for (uint32_t k = 0; k < 4; ++k) {
             if (CODE == DF_F)
@@ -59,7 +43,7 @@ PCG_DEV void rater_chunk(float* sf, uint32_t in, uint32_t h, uint32_t nx, uint32
             else
                 r.v[k] = ubits(fbits(a[q].v[k]) ^ fbits(b[q].v[k]));
         }
-        st4(sf, CODE == DF_COMB ? bp + i : nx + i, r);
+        stv<4>(sf, CODE == DF_COMB ? bp + i : nx + i, r);
     }
 }
 

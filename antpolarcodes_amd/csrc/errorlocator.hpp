@@ -22,20 +22,13 @@ constexpr inline uint32_t el_des(uint32_t N) { return 3u * N; }
 constexpr inline uint32_t el_slab_floats(uint32_t N) { return 4u * N; }
 
 struct ErrorLocatorArgs {
-    const float* llr;     // F x N channel LLRs (device)
+    LaneArgs c;           // ops: the SC-Flip schedule of one root decode; no info, ok or detector
     const float* desired; // F x N desired leaf values, or null: +0 at information leaves, +inf at frozen ones
-    uint64_t F;
-    const uint32_t* ops; // the SC-Flip schedule of one root decode (device), DF_WORDS words per op
-    uint32_t nops;
-    uint32_t N;
-    uint32_t mode;   // ErrorLocatorMode
-    float* u;        // F x N leaf values (getOutput) or null
-    uint32_t* bits;  // F x N decoded words (getSoftCodeword) or null
-    int32_t* first;  // F or null
-    uint32_t* count; // F or null
-    float* slab;          // units x 64 x slab_floats
-    uint32_t slab_floats; // words per lane (a multiple of 4)
-    uint32_t units;       // grid size (persistent waves)
+    uint32_t mode;        // ErrorLocatorMode
+    float* u;             // F x N leaf values (getOutput) or null
+    uint32_t* bits;       // F x N decoded words (getSoftCodeword) or null
+    int32_t* first;       // F or null
+    uint32_t* count;      // F or null
 };
 
 // The error-locator plan: build_depthfirst_plan's validation without the trial-limit rules (at
@@ -44,7 +37,6 @@ struct ErrorLocatorArgs {
 int build_errorlocator_plan(PlanHost& p, uint32_t N, const uint32_t* frozen, uint32_t nf, uint32_t* slab_floats,
                             std::string* err);
 
-uint32_t errorlocator_lds_bytes(uint32_t N);
 uint64_t errorlocator_wave_cap(uint32_t N, uint32_t slab_floats);
 int launch_errorlocator(const ErrorLocatorArgs& a, hipStream_t stream);
 

@@ -19,7 +19,8 @@
 // nodes of each level (level 0 = the channel LLRs), the N decoded words, and the N desired
 // values, each overwritten by its leaf's value once that leaf is done.  LLRs and desired values
 // come in, and leaf values and decoded words go out, through one LDS transpose tile, so global
-// accesses are contiguous runs of a frame's row.
+// accesses are contiguous runs of a frame's row (rows_in / rows_out of lane_frame.hpp, which also
+// has the slab access and the launch; it comes through depthfirst_ops.hpp).
 #include "errorlocator.hpp"
 
 #include "depthfirst_ops.hpp"
@@ -27,56 +28,6 @@
 namespace pcg {
 
 namespace {
-
-constexpr uint32_t TILE = 64;        // positions per transpose tile
-constexpr uint32_t TILE_STRIDE = 65; // LDS row stride of a tile (conflict-free columns)
-
-// rows [frame0, frame0 + nfr) of the F x N array `src` into words [base, base + N) of the lanes' slabs
-PCG_DEV void rows_in(uint32_t* tile, float* sf, uint32_t base, const float* src, uint64_t frame0, uint32_t nfr,
-                     uint32_t N, uint32_t T, uint32_t lane)
-{
-    for (uint32_t c = 0; c < N / T; ++c) {
-        // a wave has no other wave on its SIMD to hide a load behind: 16 rows in flight at a time
-        for (uint32_t f0 = 0; f0 < 64; f0 += 16) {
-            uint32_t v[16];
-#pragma unroll
-            for (uint32_t q = 0; q < 16; ++q)
-                v[q] = lane < T && f0 + q < nfr ? fbits(src[(frame0 + f0 + q) * N + c * T + lane]) : 0u;
-#pragma unroll
-            for (uint32_t q = 0; q < 16; ++q)
-                if (lane < T)
-                    tile[(f0 + q) * TILE_STRIDE + lane] = v[q];
-        }
-        wsync();
-        for (uint32_t j = 0; j < T; j += 4) {
-            V4 v;
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k)
-                v.v[k] = ubits(tile[lane * TILE_STRIDE + j + k]);
-            st4(sf, base + c * T + j, v);
-        }
-        wsync();
-    }
-}
-
-// words [base, base + N) of the lanes' slabs into rows [frame0, frame0 + nfr) of the F x N array `dst`
-PCG_DEV void rows_out(uint32_t* tile, const float* sf, uint32_t base, uint32_t* dst, uint64_t frame0, uint32_t nfr,
-                      uint32_t N, uint32_t T, uint32_t lane)
-{
-    for (uint32_t c = 0; c < N / T; ++c) {
-        for (uint32_t j = 0; j < T; j += 4) {
-            const V4 x = ld4(sf, base + c * T + j);
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k)
-                tile[lane * TILE_STRIDE + j + k] = fbits(x.v[k]);
-        }
-        wsync();
-        for (uint32_t f = 0; f < nfr; ++f)
-            if (lane < T)
-                dst[(frame0 + f) * N + c * T + lane] = tile[f * TILE_STRIDE + lane];
-        wsync();
-    }
-}
 
 // what a lane carries through the leaves: firstError() and correctionCount()
 struct Genie {
@@ -126,7 +77,7 @@ PCG_DEV void el_leaf8_op(float* sf, uint32_t N, uint32_t l, uint32_t group, uint
                          bool has_desired, bool want_u, Genie& g)
 {
     const uint32_t in = df_lvl(N, l), bp = df_bits(N) + group * 8u, dp = el_des(N) + group * 8u;
-    const V4 u = ld4(sf, in), v = ld4(sf, in + 4);
+    const Vec<4> u = ldv<4>(sf, in), v = ldv<4>(sf, in + 4);
     float x[8];
     uint32_t des[8], val[8], out[8];
 #pragma unroll
@@ -135,7 +86,7 @@ PCG_DEV void el_leaf8_op(float* sf, uint32_t N, uint32_t l, uint32_t group, uint
         x[4 + k] = v.v[k];
     }
     if (has_desired) {
-        const V4 d0 = ld4(sf, dp), d1 = ld4(sf, dp + 4);
+        const Vec<4> d0 = ldv<4>(sf, dp), d1 = ldv<4>(sf, dp + 4);
 #pragma unroll
         for (uint32_t k = 0; k < 4; ++k) {
             des[k] = fbits(d0.v[k]);
@@ -147,22 +98,22 @@ PCG_DEV void el_leaf8_op(float* sf, uint32_t N, uint32_t l, uint32_t group, uint
             des[k] = (mask >> k) & 1u ? 0x7f800000u : 0u;
     }
     el_small<8, 0>(x, out, mask, des, val, mode, group * 8u, g);
-    V4 r0, r1;
+    Vec<4> r0, r1;
 #pragma unroll
     for (uint32_t k = 0; k < 4; ++k) {
         r0.v[k] = ubits(out[k]);
         r1.v[k] = ubits(out[4 + k]);
     }
-    st4(sf, bp, r0);
-    st4(sf, bp + 4, r1);
+    stv<4>(sf, bp, r0);
+    stv<4>(sf, bp + 4, r1);
     if (want_u) {
 #pragma unroll
         for (uint32_t k = 0; k < 4; ++k) {
             r0.v[k] = ubits(val[k]);
             r1.v[k] = ubits(val[4 + k]);
         }
-        st4(sf, dp, r0);
-        st4(sf, dp + 4, r1);
+        stv<4>(sf, dp, r0);
+        stv<4>(sf, dp + 4, r1);
     }
 }
 
@@ -171,22 +122,22 @@ __global__ void __launch_bounds__(64) errorlocator_kernel(ErrorLocatorArgs a)
     extern __shared__ uint32_t smem_el[];
     uint32_t* tile = smem_el;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t N = a.N, mode = a.mode;
+    const uint32_t N = a.c.N, mode = a.mode;
     const uint32_t T = N < TILE ? N : TILE;
-    float* sf = a.slab + (uint64_t)blockIdx.x * a.slab_floats * 64u + lane * 4u;
+    float* sf = a.c.slab + (uint64_t)blockIdx.x * a.c.slab_floats * 64u + lane * 4u;
     const bool has_desired = a.desired != nullptr, want_u = a.u != nullptr;
-    const uint64_t ngroups = (a.F + 63) / 64;
+    const uint64_t ngroups = (a.c.F + 63) / 64;
     for (uint64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
         const uint64_t frame0 = grp * 64, frame = frame0 + lane;
-        const uint32_t nfr = a.F - frame0 < 64 ? (uint32_t)(a.F - frame0) : 64u;
-        rows_in(tile, sf, 0, a.llr, frame0, nfr, N, T, lane);
+        const uint32_t nfr = a.c.F - frame0 < 64 ? (uint32_t)(a.c.F - frame0) : 64u;
+        rows_in(tile, sf, 0, a.c.llr, frame0, nfr, N, T, lane);
         if (has_desired)
             rows_in(tile, sf, el_des(N), a.desired, frame0, nfr, N, T, lane);
         Genie g;
         g.first = -1;
         g.count = 0;
-        for (uint32_t k = 0; k < a.nops; ++k) {
-            const uint32_t op = ld_const(a.ops, DF_WORDS * k);
+        for (uint32_t k = 0; k < a.c.nops; ++k) {
+            const uint32_t op = ld_const(a.c.ops, DF_WORDS * k);
             const uint32_t code = scan_code(op), l = scan_level(op), grpn = scan_group(op);
             if (code == DF_F)
                 rater_op<DF_F>(sf, N, l, grpn);
@@ -204,42 +155,22 @@ __global__ void __launch_bounds__(64) errorlocator_kernel(ErrorLocatorArgs a)
                 a.count[frame] = g.count;
         }
         if (want_u)
-            rows_out(tile, sf, el_des(N), reinterpret_cast<uint32_t*>(a.u), frame0, nfr, N, T, lane);
+            rows_out(tile, sf, el_des(N), reinterpret_cast<uint32_t*>(a.u), frame0, nfr, N, T, lane, ~0ull);
         if (a.bits)
-            rows_out(tile, sf, df_bits(N), a.bits, frame0, nfr, N, T, lane);
+            rows_out(tile, sf, df_bits(N), a.bits, frame0, nfr, N, T, lane, ~0ull);
     }
 }
 
 } // namespace
 
-uint32_t errorlocator_lds_bytes(uint32_t) { return 4u * TILE * TILE_STRIDE; }
-
-// Persistent waves of a launch: up to 4 per CU (one per SIMD) as far as they are resident, and
-// as many as keep the slab within 2 GiB.
 uint64_t errorlocator_wave_cap(uint32_t N, uint32_t slab_floats)
 {
-    int dev = 0, cus = 256, res = 0;
-    if (hipGetDevice(&dev) == hipSuccess)
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&res, errorlocator_kernel, 64, errorlocator_lds_bytes(N)) !=
-        hipSuccess)
-        res = 0;
-    uint64_t wpc = res > 0 ? (uint64_t)res : 1;
-    if (wpc > 4)
-        wpc = 4;
-    uint64_t cap = (uint64_t)cus * wpc;
-    const uint64_t fit = (2ull << 30) / (256ull * slab_floats);
-    if (cap > fit)
-        cap = fit ? fit : 1;
-    return cap;
+    return lane_wave_cap(errorlocator_kernel, lane_lds_bytes(N, false), 256ull * slab_floats);
 }
 
 int launch_errorlocator(const ErrorLocatorArgs& a, hipStream_t stream)
 {
-    if (a.units == 0)
-        return a.F ? -4 : 0;
-    hipLaunchKernelGGL(errorlocator_kernel, dim3(a.units), dim3(64), (size_t)errorlocator_lds_bytes(a.N), stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return lane_launch(errorlocator_kernel, a, lane_lds_bytes(a.c.N, false), stream);
 }
 
 } // namespace pcg

@@ -36,24 +36,11 @@ constexpr inline uint32_t fsscan_el(uint32_t N) { return 2u * N; }
 constexpr inline uint32_t fsscan_er(uint32_t N) { return 4u * N; }
 
 struct FsscanArgs {
-    const float* llr; // F x N channel LLRs (device)
-    uint64_t F;
-    const uint32_t* ops; // flattened schedule of one pass (device), FSS_WORDS words per op
-    uint32_t nops;
-    uint32_t N, K, kb;
+    LaneArgs c;       // ops: the schedule of one pass, FSS_WORDS words per op
     uint32_t trials;  // trial limit, 1 .. 255
     int forced;       // run exactly `trials` passes; the check only after the last
-    const uint16_t* info_pos;
-    uint32_t crc_c0;
-    uint32_t crc_bits;
-    const uint32_t* crc_rows; // as KernelArgs::crc_rows
-    uint8_t* info;      // F x kb
-    uint8_t* ok;        // F or null
-    float* soft;        // F x N or null
-    uint8_t* ntrials;   // F or null: passes run
-    float* slab;        // units x 64 x slab_floats
-    uint32_t slab_floats; // floats per lane (a multiple of 4)
-    uint32_t units;     // grid size (persistent waves)
+    float* soft;      // F x N or null
+    uint8_t* ntrials; // F or null: passes run
 };
 
 // The Fast-SSCAN plan: validation, info positions and detector model as build_plan; `ops` =
@@ -63,7 +50,6 @@ enum FsscanNode : int { FSS_NODE_RATER = 0, FSS_NODE_ZERO = 1, FSS_NODE_ONE = 2,
 int build_fsscan_plan(PlanHost& p, uint32_t N, const uint32_t* frozen, uint32_t nf, int systematic, int crc_kind,
                       uint32_t* slab_floats, std::string* err);
 
-uint32_t fsscan_lds_bytes(uint32_t N);
 uint64_t fsscan_wave_cap(uint32_t N, uint32_t slab_floats);
 int launch_fsscan(const FsscanArgs& a, hipStream_t stream);
 

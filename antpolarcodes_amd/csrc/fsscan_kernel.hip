@@ -19,42 +19,17 @@
 // A pass is repeated while the frame's detector check fails, up to the trial limit; a wave runs
 // until all of its lanes have passed.  A lane that has passed keeps computing with the wave, but
 // its outputs are stored only in passes it still needed.
+//
+// The tile's store to frame rows, the slab access (Vec / ldv / stv), the detector syndrome, the
+// information bytes and the launch are lane_frame.hpp's; the fused "soft = llr + root message,
+// sign bits" loop in front of the soft codeword's store and the channel load stay here.
 #include "fsscan.hpp"
-#include "wave.hpp"
+#include "lane_frame.hpp"
 
 namespace pcg {
 
 namespace {
 
-constexpr uint32_t TILE = 64;        // positions per transpose tile
-constexpr uint32_t TILE_STRIDE = 65; // LDS row stride of a tile (conflict-free columns)
-
-// W consecutive values of a lane at slab offset `off` (a multiple of W; W = 4 or 2)
-template <uint32_t W>
-struct Vec {
-    float v[W];
-};
-template <uint32_t W>
-PCG_DEV Vec<W> ldv(const float* sf, uint32_t off)
-{
-    Vec<W> r;
-    if constexpr (W == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(sf + (uint64_t)off * 64u);
-        r.v[0] = t.x, r.v[1] = t.y, r.v[2] = t.z, r.v[3] = t.w;
-    } else {
-        const float2 t = *reinterpret_cast<const float2*>(sf + (uint64_t)(off >> 2) * 256u + (off & 3u));
-        r.v[0] = t.x, r.v[1] = t.y;
-    }
-    return r;
-}
-template <uint32_t W>
-PCG_DEV void stv(float* sf, uint32_t off, const Vec<W>& r)
-{
-    if constexpr (W == 4)
-        *reinterpret_cast<float4*>(sf + (uint64_t)off * 64u) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    else
-        *reinterpret_cast<float2*>(sf + (uint64_t)(off >> 2) * 256u + (off & 3u)) = make_float2(r.v[0], r.v[1]);
-}
 template <uint32_t W>
 PCG_DEV Vec<W> splat(float c)
 {
@@ -169,24 +144,28 @@ PCG_DEV void rep_op(float* sf, uint32_t in, uint32_t n, uint32_t dst)
 __global__ void __launch_bounds__(64) fsscan_kernel(FsscanArgs a)
 {
     extern __shared__ uint32_t smem_fsscan[];
-    float* tile = reinterpret_cast<float*>(smem_fsscan);
+    uint32_t* tile = smem_fsscan;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t N = a.N;
+    const uint32_t N = a.c.N;
     const uint32_t T = N < TILE ? N : TILE;
     const uint32_t W = N >= 32 ? N / 32 : 1u;
     uint32_t* row = smem_fsscan + TILE * TILE_STRIDE + lane; // own sign-bit row, word q at [q * 64]
-    float* sf = a.slab + (uint64_t)blockIdx.x * a.slab_floats * 64u + lane * 4u;
+    float* sf = a.c.slab + (uint64_t)blockIdx.x * a.c.slab_floats * 64u + lane * 4u;
     const uint32_t IN0 = 0, OUT0 = fsscan_el(N); // channel LLRs, the root's message
-    const uint64_t ngroups = (a.F + 63) / 64;
-    const bool aligned = (reinterpret_cast<uintptr_t>(a.llr) & 15u) == 0; // rows are N * 4 bytes, N >= 8
+    const uint64_t ngroups = (a.c.F + 63) / 64;
+    const bool aligned = (reinterpret_cast<uintptr_t>(a.c.llr) & 15u) == 0; // rows are N * 4 bytes, N >= 8
     for (uint64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
         const uint64_t frame0 = grp * 64, frame = frame0 + lane;
-        const uint32_t nfr = a.F - frame0 < 64 ? (uint32_t)(a.F - frame0) : 64u;
+        const uint32_t nfr = a.c.F - frame0 < 64 ? (uint32_t)(a.c.F - frame0) : 64u;
         // channel LLRs into level 0.  Rows that are 16-byte aligned: every lane reads its own frame,
         // eight float4 in flight (the loads of a wave are what a one-wave-per-CU launch waits for:
-        // 32 round trips at N = 1024 instead of the tile's 1024 row loads); else through the tile
+        // 32 round trips at N = 1024 instead of the tile's 1024 row loads); else through the tile, one
+        // row load at a time.  Both stay here (not lane_frame.hpp's rows_in_own / rows_in): with
+        // rows_in the scalar registers of its 16 loads in flight were spilled inside the passes'
+        // loops, +3 % per pass, and with rows_in_own a one-pass decode still measured 0.2 - 0.4 %
+        // over its bound (profiles/lane_frame_refactor.txt)
         if (aligned) {
-            const float4* src = reinterpret_cast<const float4*>(a.llr + (lane < nfr ? frame : frame0) * N);
+            const float4* src = reinterpret_cast<const float4*>(a.c.llr + (lane < nfr ? frame : frame0) * N);
             for (uint32_t e = 0; e < N; e += 32) { // N is a multiple of 8: the tail is two float4
                 float4 v[8];
 #pragma unroll
@@ -203,13 +182,13 @@ __global__ void __launch_bounds__(64) fsscan_kernel(FsscanArgs a)
         for (uint32_t c = 0; !aligned && c < N / T; ++c) {
             for (uint32_t f = 0; f < 64; ++f)
                 if (lane < T)
-                    tile[f * TILE_STRIDE + lane] = f < nfr ? a.llr[(frame0 + f) * N + c * T + lane] : 0.0f;
+                    tile[f * TILE_STRIDE + lane] = f < nfr ? fbits(a.c.llr[(frame0 + f) * N + c * T + lane]) : 0u;
             wsync();
             for (uint32_t j = 0; j < T; j += 4) {
                 Vec<4> v;
 #pragma unroll
                 for (uint32_t k = 0; k < 4; ++k)
-                    v.v[k] = tile[lane * TILE_STRIDE + j + k];
+                    v.v[k] = ubits(tile[lane * TILE_STRIDE + j + k]);
                 stv<4>(sf, IN0 + c * T + j, v);
             }
             wsync();
@@ -217,9 +196,9 @@ __global__ void __launch_bounds__(64) fsscan_kernel(FsscanArgs a)
         bool done = lane >= nfr; // passed its check in an earlier pass (or no frame)
         for (uint32_t pass = 1; pass <= a.trials; ++pass) {
             const bool first = pass == 1;
-            for (uint32_t k = 0; k < a.nops; ++k) {
-                const uint32_t op = ld_const(a.ops, FSS_WORDS * k), er = ld_const(a.ops, FSS_WORDS * k + 1),
-                               own = ld_const(a.ops, FSS_WORDS * k + 2);
+            for (uint32_t k = 0; k < a.c.nops; ++k) {
+                const uint32_t op = ld_const(a.c.ops, FSS_WORDS * k), er = ld_const(a.c.ops, FSS_WORDS * k + 1),
+                               own = ld_const(a.c.ops, FSS_WORDS * k + 2);
                 const uint32_t code = scan_code(op), l = scan_level(op), fl = scan_flags(op);
                 if (code == FSS_LEFT) {
                     rater_op<FSS_LEFT>(sf, N, l, fl, er, own, first);
@@ -256,50 +235,22 @@ __global__ void __launch_bounds__(64) fsscan_kernel(FsscanArgs a)
                         const float v = x.v[k] + m.v[k];
                         bits |= (fbits(v) >> 31) << ((j + k) & 31u);
                         if (a.soft)
-                            tile[lane * TILE_STRIDE + j + k] = v;
+                            tile[lane * TILE_STRIDE + j + k] = fbits(v);
                     }
                     if (((j + 3) & 31u) == 31u || j + 4 == T) {
                         row[((c * T + j) >> 5) << 6] = bits;
                         bits = 0;
                     }
                 }
-                if (a.soft) {
-                    wsync();
-                    for (uint32_t f = 0; f < nfr; ++f)
-                        if (((livem >> f) & 1u) && lane < T)
-                            a.soft[(frame0 + f) * N + c * T + lane] = tile[f * TILE_STRIDE + lane];
-                    wsync();
-                }
+                if (a.soft)
+                    tile_out(tile, reinterpret_cast<uint32_t*>(a.soft), frame0, nfr, N, c, T, lane, livem);
             }
-            // detector syndrome and info bytes from the sign bits (as scan_kernel)
-            uint32_t syn = a.crc_c0;
-            for (uint32_t rb = 0; rb < a.crc_bits; ++rb) {
-                uint32_t pc = 0;
-                for (uint32_t q = 0; q < W; ++q)
-                    pc += __builtin_popcount(row[q << 6] & a.crc_rows[rb * W + q]);
-                syn ^= (pc & 1u) << rb;
-            }
-            const bool pass_ok = syn == 0;
+            // detector syndrome and info bytes from the sign bits
+            const bool pass_ok = detector_syndrome(row, W, a.c.crc_c0, a.c.crc_bits, a.c.crc_rows) == 0;
             if (live && (a.forced || pass_ok || last)) { // this lane's final pass
-                uint8_t* out = a.info + frame * a.kb;
-                uint32_t cw = 0xffffffffu, word = 0;
-                for (uint32_t b = 0; b < a.kb; ++b) {
-                    uint32_t byte = 0;
-                    for (uint32_t q = 0; q < 8; ++q) {
-                        const uint32_t idx = 8 * b + q;
-                        if (idx < a.K) {
-                            const uint32_t pos = a.info_pos[idx];
-                            if ((pos >> 5) != cw) {
-                                cw = pos >> 5;
-                                word = row[cw << 6];
-                            }
-                            byte |= ((word >> (pos & 31u)) & 1u) << (7 - q);
-                        }
-                    }
-                    out[b] = (uint8_t)byte;
-                }
-                if (a.ok)
-                    a.ok[frame] = pass_ok ? 1 : 0;
+                store_info_bytes(row, a.c.info_pos, a.c.K, a.c.kb, a.c.info + frame * a.c.kb);
+                if (a.c.ok)
+                    a.c.ok[frame] = pass_ok ? 1 : 0;
                 if (a.ntrials)
                     a.ntrials[frame] = (uint8_t)pass;
             }
@@ -314,33 +265,14 @@ __global__ void __launch_bounds__(64) fsscan_kernel(FsscanArgs a)
 
 } // namespace
 
-uint32_t fsscan_lds_bytes(uint32_t N) { return 4u * (TILE * TILE_STRIDE + 64u * (N >= 32 ? N / 32 : 1u)); }
-
-// Persistent waves of a launch: up to 4 per CU (one per SIMD) as far as they are resident, and
-// as many as keep the slab within 2 GiB.
 uint64_t fsscan_wave_cap(uint32_t N, uint32_t slab_floats)
 {
-    int dev = 0, cus = 256, res = 0;
-    if (hipGetDevice(&dev) == hipSuccess)
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&res, fsscan_kernel, 64, fsscan_lds_bytes(N)) != hipSuccess)
-        res = 0;
-    uint64_t wpc = res > 0 ? (uint64_t)res : 1;
-    if (wpc > 4)
-        wpc = 4;
-    uint64_t cap = (uint64_t)cus * wpc;
-    const uint64_t fit = (2ull << 30) / (256ull * slab_floats);
-    if (cap > fit)
-        cap = fit ? fit : 1;
-    return cap;
+    return lane_wave_cap(fsscan_kernel, lane_lds_bytes(N, true), 256ull * slab_floats);
 }
 
 int launch_fsscan(const FsscanArgs& a, hipStream_t stream)
 {
-    if (a.units == 0)
-        return a.F ? -4 : 0;
-    hipLaunchKernelGGL(fsscan_kernel, dim3(a.units), dim3(64), (size_t)fsscan_lds_bytes(a.N), stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return lane_launch(fsscan_kernel, a, lane_lds_bytes(a.c.N, true), stream);
 }
 
 } // namespace pcg

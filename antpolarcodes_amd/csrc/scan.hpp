@@ -29,24 +29,32 @@ constexpr inline uint32_t scan_flags(uint32_t w) { return w >> 24; }
 
 constexpr uint32_t SCAN_MAX_N = 4096;
 
-struct ScanArgs {
+// What every lane = codeword kernel is given (lane_frame.hpp); the first member `c` of the
+// kernels' argument structs.  The error locator has no detector and no information bytes.
+struct LaneArgs {
     const float* llr; // F x N channel LLRs (device)
     uint64_t F;
-    const uint32_t* ops; // flattened schedule of one iteration (device)
+    const uint32_t* ops; // flattened schedule (device)
     uint32_t nops;
-    uint32_t N, log2N, K, kb;
-    uint32_t iters;
+    uint32_t N, K, kb;
     const uint16_t* info_pos; // K info positions (device)
     uint32_t crc_c0;
     uint32_t crc_bits;
     const uint32_t* crc_rows; // as KernelArgs::crc_rows
+    uint8_t* info;        // F x kb
+    uint8_t* ok;          // F or null
+    float* slab;          // units x 64 x slab_floats
+    uint32_t slab_floats; // words per lane (a multiple of 4)
+    uint32_t units;       // grid size (persistent waves)
+};
+
+struct ScanArgs {
+    LaneArgs c; // ops: ScanOp words of one iteration; slab_floats = scan_slab_floats / 64
+    uint32_t log2N;
+    uint32_t iters;
     int systematic;
-    uint8_t* info;   // F x kb
-    uint8_t* ok;     // F or null
-    float* soft;     // F x N or null
-    float* ext;      // F x N or null
-    float* slab;     // units x scan_slab_floats(N, systematic)
-    uint32_t units;  // grid size (persistent waves)
+    float* soft; // F x N or null
+    float* ext;  // F x N or null
 };
 
 // The SCAN plan: validation, info positions and detector model as build_plan, `ops` = ScanOp
@@ -55,10 +63,9 @@ struct PlanHost;
 int build_scan_plan(PlanHost& p, uint32_t N, const uint32_t* frozen, uint32_t nf, int systematic, int crc_kind,
                     std::string* err);
 
-// floats of global state one wave (64 codewords) keeps; LDS bytes of a wave
+// floats of global state one wave (64 codewords) keeps
 uint64_t scan_slab_floats(uint32_t N, int systematic);
-uint32_t scan_lds_bytes(uint32_t N);
-uint64_t scan_wave_cap(uint32_t N, int systematic);
+uint64_t scan_wave_cap(uint32_t N, uint32_t slab_floats); // slab_floats: per lane, as LaneArgs
 int launch_scan(const ScanArgs& a, hipStream_t stream);
 
 } // namespace pcg

@@ -21,18 +21,14 @@
 // finite LLRs, which the ops of their parents take as constants (SCAN_EINF / SCAN_OINF) -- in the
 // first iteration a right all-frozen child's message is still the initial +0 where its left
 // sibling reads it, as in the reference.
-#include "scan.hpp"
-#include "wave.hpp"
-
-#include <stdio.h>
-#include <stdlib.h>
+//
+// Frame rows in and out through the transpose tile, the detector syndrome, the information bytes
+// and the launch are lane_frame.hpp's; the bit reversal between a row and the slab stays here.
+#include "lane_frame.hpp"
 
 namespace pcg {
 
 namespace {
-
-constexpr uint32_t TILE = 64;          // positions per transpose tile
-constexpr uint32_t TILE_STRIDE = 65;   // LDS row stride of a tile (conflict-free columns)
 
 PCG_DEV uint32_t bitrev(uint32_t v, uint32_t nbits) { return __builtin_bitreverse32(v) >> (32u - nbits); }
 
@@ -121,9 +117,9 @@ PCG_DEV void node_op(const Wave& w, uint32_t l, uint32_t g, uint32_t flags, bool
 __global__ void __launch_bounds__(64) scan_kernel(ScanArgs a)
 {
     extern __shared__ uint32_t smem_scan[];
-    float* tile = reinterpret_cast<float*>(smem_scan);
+    uint32_t* tile = smem_scan;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t N = a.N, n = a.log2N;
+    const uint32_t N = a.c.N, n = a.log2N;
     const uint32_t T = N < TILE ? N : TILE;
     const uint32_t W = N >= 32 ? N / 32 : 1u;
     uint32_t* row = smem_scan + TILE * TILE_STRIDE + lane; // own sign-bit row, word q at [q * 64]
@@ -131,29 +127,26 @@ __global__ void __launch_bounds__(64) scan_kernel(ScanArgs a)
     w.N = N;
     w.n = n;
     w.ly = scan_layout(N, n, a.systematic);
-    w.s = reinterpret_cast<float2*>(a.slab) + (uint64_t)blockIdx.x * w.ly.units * 64u + lane;
+    w.s = reinterpret_cast<float2*>(a.c.slab) + (uint64_t)blockIdx.x * w.ly.units * 64u + lane;
     float* sf = reinterpret_cast<float*>(w.s); // element e of unit u at sf[u * 128 + e]
     const float inf = __builtin_inff();
-    const uint64_t ngroups = (a.F + 63) / 64;
+    const uint64_t ngroups = (a.c.F + 63) / 64;
     for (uint64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
         const uint64_t frame0 = grp * 64, frame = frame0 + lane;
-        const uint32_t nfr = a.F - frame0 < 64 ? (uint32_t)(a.F - frame0) : 64u;
+        const uint32_t nfr = a.c.F - frame0 < 64 ? (uint32_t)(a.c.F - frame0) : 64u;
         // channel LLRs into level 0, bit-reversed (scan.cpp:229-233), transposed through LDS
         for (uint32_t c = 0; c < N / T; ++c) {
-            for (uint32_t f = 0; f < 64; ++f)
-                if (lane < T)
-                    tile[f * TILE_STRIDE + lane] = f < nfr ? a.llr[(frame0 + f) * N + c * T + lane] : 0.0f;
-            wsync();
+            tile_in(tile, a.c.llr, frame0, nfr, N, c, T, lane);
             for (uint32_t j = 0; j < T; ++j) {
                 const uint32_t r = bitrev(c * T + j, n);
-                sf[(uint64_t)(w.ly.L + (r >> 1)) * 128u + (r & 1u)] = tile[lane * TILE_STRIDE + j];
+                sf[(uint64_t)(w.ly.L + (r >> 1)) * 128u + (r & 1u)] = ubits(tile[lane * TILE_STRIDE + j]);
             }
             wsync();
         }
         for (uint32_t it = 0; it < a.iters; ++it) {
             const bool first = it == 0;
-            for (uint32_t k = 0; k < a.nops; ++k) {
-                const uint32_t op = ld_const(a.ops, k);
+            for (uint32_t k = 0; k < a.c.nops; ++k) {
+                const uint32_t op = ld_const(a.c.ops, k);
                 const uint32_t code = scan_code(op), l = scan_level(op), g = scan_group(op), fl = scan_flags(op);
                 if (code == SCAN_DOWN_L) {
                     node_op<SCAN_DOWN_L>(w, l, g, fl, first);
@@ -196,57 +189,26 @@ __global__ void __launch_bounds__(64) scan_kernel(ScanArgs a)
                     bits = 0;
                 }
                 if (a.soft)
-                    tile[lane * TILE_STRIDE + j] = v;
+                    tile[lane * TILE_STRIDE + j] = fbits(v);
             }
-            if (a.soft) {
-                wsync();
-                for (uint32_t f = 0; f < nfr; ++f)
-                    if (lane < T)
-                        a.soft[(frame0 + f) * N + c * T + lane] = tile[f * TILE_STRIDE + lane];
-                wsync();
-            }
+            if (a.soft)
+                tile_out(tile, reinterpret_cast<uint32_t*>(a.soft), frame0, nfr, N, c, T, lane, ~0ull);
         }
         if (a.ext)
             for (uint32_t c = 0; c < N / T; ++c) {
                 for (uint32_t j = 0; j < T; ++j) {
                     const uint32_t r = bitrev(c * T + j, n);
                     tile[lane * TILE_STRIDE + j] =
-                        a.iters ? sf[(uint64_t)w.ly.E * 128u + (uint64_t)(r >> 1) * 128u + (r & 1u)] : 0.0f;
+                        a.iters ? fbits(sf[(uint64_t)w.ly.E * 128u + (uint64_t)(r >> 1) * 128u + (r & 1u)]) : 0u;
                 }
-                wsync();
-                for (uint32_t f = 0; f < nfr; ++f)
-                    if (lane < T)
-                        a.ext[(frame0 + f) * N + c * T + lane] = tile[f * TILE_STRIDE + lane];
-                wsync();
+                tile_out(tile, reinterpret_cast<uint32_t*>(a.ext), frame0, nfr, N, c, T, lane, ~0ull);
             }
-        // detector syndrome and info bytes from the sign bits (as scs_kernel.hip)
-        uint32_t syn = a.crc_c0;
-        for (uint32_t rb = 0; rb < a.crc_bits; ++rb) {
-            uint32_t pc = 0;
-            for (uint32_t q = 0; q < W; ++q)
-                pc += __builtin_popcount(row[q << 6] & a.crc_rows[rb * W + q]);
-            syn ^= (pc & 1u) << rb;
-        }
-        if (frame < a.F) {
-            uint8_t* out = a.info + frame * a.kb;
-            uint32_t cw = 0xffffffffu, word = 0;
-            for (uint32_t b = 0; b < a.kb; ++b) {
-                uint32_t byte = 0;
-                for (uint32_t q = 0; q < 8; ++q) {
-                    const uint32_t idx = 8 * b + q;
-                    if (idx < a.K) {
-                        const uint32_t pos = a.info_pos[idx];
-                        if ((pos >> 5) != cw) {
-                            cw = pos >> 5;
-                            word = row[cw << 6];
-                        }
-                        byte |= ((word >> (pos & 31u)) & 1u) << (7 - q);
-                    }
-                }
-                out[b] = (uint8_t)byte;
-            }
-            if (a.ok)
-                a.ok[frame] = syn == 0 ? 1 : 0;
+        // detector syndrome and info bytes from the sign bits
+        const uint32_t syn = detector_syndrome(row, W, a.c.crc_c0, a.c.crc_bits, a.c.crc_rows);
+        if (frame < a.c.F) {
+            store_info_bytes(row, a.c.info_pos, a.c.K, a.c.kb, a.c.info + frame * a.c.kb);
+            if (a.c.ok)
+                a.c.ok[frame] = syn == 0 ? 1 : 0;
         }
     }
 }
@@ -258,33 +220,14 @@ uint64_t scan_slab_floats(uint32_t N, int systematic)
     return 128ull * scan_layout(N, (uint32_t)__builtin_ctz(N), systematic).units;
 }
 
-uint32_t scan_lds_bytes(uint32_t N) { return 4u * (TILE * TILE_STRIDE + 64u * (N >= 32 ? N / 32 : 1u)); }
-
-// Persistent waves of a launch: up to 4 per CU (one per SIMD) as far as they are resident, and
-// as many as keep the slab within 2 GiB.
-uint64_t scan_wave_cap(uint32_t N, int systematic)
+uint64_t scan_wave_cap(uint32_t N, uint32_t slab_floats)
 {
-    int dev = 0, cus = 256, res = 0;
-    if (hipGetDevice(&dev) == hipSuccess)
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&res, scan_kernel, 64, scan_lds_bytes(N)) != hipSuccess)
-        res = 0;
-    uint64_t wpc = res > 0 ? (uint64_t)res : 1;
-    if (wpc > 4)
-        wpc = 4;
-    uint64_t cap = (uint64_t)cus * wpc;
-    const uint64_t fit = (2ull << 30) / (4ull * scan_slab_floats(N, systematic));
-    if (cap > fit)
-        cap = fit ? fit : 1;
-    return cap;
+    return lane_wave_cap(scan_kernel, lane_lds_bytes(N, true), 256ull * slab_floats);
 }
 
 int launch_scan(const ScanArgs& a, hipStream_t stream)
 {
-    if (a.units == 0)
-        return a.F ? -4 : 0;
-    hipLaunchKernelGGL(scan_kernel, dim3(a.units), dim3(64), (size_t)scan_lds_bytes(a.N), stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return lane_launch(scan_kernel, a, lane_lds_bytes(a.c.N, true), stream);
 }
 
 } // namespace pcg
