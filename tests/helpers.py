@@ -45,6 +45,229 @@ def reference_digest(name):
         return json.load(fh)["cases"][name]
 
 
+# ---------------------------------------------------------------- adaptive decoders: batches
+# whose first stage fails exactly where a mask says (tests/test_adaptive_batches.py proves the
+# masks on the CPU, tests/test_gpu_adaptive_edges.py decodes them)
+
+# name -> (N, K, L, crc); BB construction at 0 dB
+ADAPTIVE_CODES = {
+    "n32_l2": (32, 16, 2, 8),
+    "n64_l32": (64, 32, 32, 16),
+    "n256_l4": (256, 128, 4, 8),
+    "n256_l6": (256, 128, 6, 32),
+    "n1024_l8": (1024, 512, 8, 8),
+}
+
+ADAPTIVE_PATTERNS = ("none", "all", "one_frame_pass", "one_frame_fail", "first", "last", "tail_lane",
+                     "g_minus", "g", "g_plus", "full_wave", "alternate")
+
+
+def list_group(L):
+    """Codewords per list wave: 64 / (L rounded up to a power of two)."""
+    lp = 1
+    while lp < L:
+        lp *= 2
+    return 64 // lp
+
+
+def adaptive_pattern(name, L, seed=0):
+    """The failure mask of one named pattern for list size L."""
+    G = list_group(L)
+
+    def at(F, idx):
+        m = np.zeros(F, bool)
+        m[np.asarray(idx, np.int64)] = True
+        return m
+
+    if name == "none":
+        return np.zeros(130, bool)
+    if name == "all":
+        return np.ones(130, bool)
+    if name == "one_frame_pass":
+        return np.zeros(1, bool)
+    if name == "one_frame_fail":
+        return np.ones(1, bool)
+    if name == "first":
+        return at(130, [0])
+    if name == "last":
+        return at(130, [129])
+    if name == "tail_lane":  # the only lane of the compaction's partial second wave
+        return at(65, [64])
+    if name in ("g_minus", "g", "g_plus"):  # around one full list wave, spread over the batch
+        n = G + {"g_minus": -1, "g": 0, "g_plus": 1}[name]
+        return at(200, np.random.default_rng(1000 + seed).permutation(200)[:n])
+    if name == "full_wave":  # one first-stage wave all ones, its neighbours none
+        return at(192, np.arange(64, 128))
+    if name == "alternate":
+        return at(129, np.arange(0, 129, 2))
+    raise ValueError(name)
+
+
+def host_chunk_mask(L, seed=0):
+    """200 frames for host chunks of 64: the first chunk a g_plus spread, the second without a
+    failure, the third failing throughout, of the last (8 frames) only its last frame."""
+    m = np.zeros(200, bool)
+    m[np.random.default_rng(2000 + seed).permutation(64)[:list_group(L) + 1]] = True
+    m[128:192] = True
+    m[199] = True
+    return m
+
+
+def sequence_masks(L):
+    """The calls of one plan in a row: g_plus, all, none (after all: a stale list), one failing
+    frame, a batch that regrows the list buffers, none."""
+    return [adaptive_pattern("g_plus", L), np.ones(64, bool), np.zeros(64, bool), np.ones(1, bool),
+            np.arange(777) % 2 == 0, np.zeros(200, bool)]
+
+
+def stream_masks(L):
+    """The calls two streams alternate on one plan: first, all, last, none."""
+    return [adaptive_pattern(n, L) for n in ("first", "all", "last", "none")]
+
+
+def rounds_frames(L, cus):
+    """A failure list of three launch rounds for some waves and a partial last group, when the
+    list stage launches `cus` waves."""
+    return list_group(L) * (2 * cus + 3) + 1
+
+
+SPECIALISED_PATTERNS = ("none", "all", "last", "g_plus")  # run on the catalogue's (1024, L 8, CRC-8) kernels
+ROUNDS_CODE = (64, 32, 32, 32)  # (N, K, L, crc) of the lists longer than one launch round: G = 2
+
+_adaptive_cache = {}
+
+
+def _assert_first_stage(ok, mask):
+    bad = np.nonzero((ok == 0) != mask)[0]
+    assert bad.size == 0, f"the first stage's verdict differs from the mask at frames {bad[:8]}"
+
+
+def _first_stage(oracle, N, frozen, rows, crc, fixed, systematic):
+    dec = oracle.scc_decode if fixed else oracle.sc_decode
+    return dec(N, frozen, rows, systematic, crc)
+
+
+def _to_i8(llr):
+    return np.clip(np.rint(llr * 10.0), -128, 127).astype(np.int8)
+
+
+def _adaptive_pool(oracle, N, frozen, crc, fixed, systematic, seed, draw):
+    """Rows at 1 dB then 5 dB Eb/N0 and the first stage's verdict on each (ok == 0: fails)."""
+    from antpolarcodes_amd import frames
+    key = ("pool", N, tuple(frozen), crc, fixed, systematic, seed, draw)
+    if key not in _adaptive_cache:
+        s = seed + 100 * draw
+        llr = np.concatenate([frames.awgn_frames(N, frozen, 300, ebn0, seed=s + k, crc=crc, systematic=systematic)[0]
+                              for ebn0, k in ((1.0, 11), (5.0, 12))])
+        _, ok = _first_stage(oracle, N, frozen, _to_i8(llr) if fixed else llr, crc, fixed, systematic)
+        _adaptive_cache[key] = (llr, ok == 0)
+    return _adaptive_cache[key]
+
+
+def adaptive_batch(oracle, N, frozen, L, crc, mask, fixed=False, systematic=True, seed=0, pool_crc=None):
+    """Inputs and expected outputs of len(mask) frames whose first stage (Fast-SSC, fixed: the
+    8-bit one on int8 rows) fails exactly where `mask` is true.
+
+    Rows come from a pool of 300 AWGN frames at 1 dB followed by 300 at 5 dB, classified by the
+    oracle's first stage: masked rows from the failing ones in pool order, the others from the
+    passing ones (rows repeat when the mask needs more than the pool has; an empty class draws
+    further pools).  A mask that fails throughout with CRC-32 takes noise-only rows instead.
+    pool_crc: draw and classify the pool with this other detector and take every row from its
+    failing rows (with crc = 0 none of them reaches the list stage).
+
+    Returns a namespace: llr (float32 rows), x8 (their int8 form clip(rint(10 llr)), fixed only),
+    frames (what the decoder is given: x8 or llr), info, ok, metrics (float32: 0 where the
+    first stage passes; 8-bit metrics are the integers as float32) and mask.
+
+    Asserted here, on the CPU: the first stage's verdict on the assembled batch is `mask`, and
+    from 16 failing rows on both list outcomes occur among them.  Noise rows are exempt from
+    the second: a CRC-32 over noise passes on a list of L with probability L / 2^32, so their
+    list stage fails throughout."""
+    from types import SimpleNamespace
+    mask = np.asarray(mask, bool)
+    key = ("batch", N, tuple(frozen), L, crc, mask.tobytes(), fixed, systematic, seed, pool_crc)
+    if key in _adaptive_cache:
+        return _adaptive_cache[key]
+    F, nfail = len(mask), int(mask.sum())
+    noise = F > 0 and nfail == F and crc == 32 and pool_crc is None
+    if noise:
+        llr = np.random.default_rng(seed + 13).normal(0, 2, (F, N)).astype(np.float32)
+    else:
+        llrs, fails = [], []
+        for draw in range(8):
+            pl, pf = _adaptive_pool(oracle, N, frozen, crc if pool_crc is None else pool_crc, fixed, systematic,
+                                    seed, draw)
+            llrs.append(pl)
+            fails.append(pf)
+            pf = np.concatenate(fails)
+            if pool_crc is not None:
+                short = not pf.any()
+            else:
+                short = (nfail > 0 and not pf.any()) or (nfail < F and pf.all())
+            if not short:
+                break
+        assert not short, "eight pools without a row of a class the mask needs"
+        pl = np.concatenate(llrs)
+        bad, good = np.nonzero(pf)[0], np.nonzero(~pf)[0]
+        if pool_crc is not None:
+            good = bad
+        rows = np.zeros(F, np.int64)
+        if nfail:
+            rows[mask] = bad[np.arange(nfail) % len(bad)]
+        if nfail < F:
+            rows[~mask] = good[np.arange(F - nfail) % len(good)]
+        llr = np.ascontiguousarray(pl[rows])
+    x8 = _to_i8(llr) if fixed else None
+    if fixed:  # float frames given to an 8-bit plan (scaled by 10) quantise to the same bytes
+        assert np.array_equal(oracle.f32_to_i8(llr * 10.0, N), x8)
+    frames_in = x8 if fixed else llr
+    info, ok = _first_stage(oracle, N, frozen, frames_in, crc, fixed, systematic)
+    info, ok = info.copy(), ok.copy()
+    _assert_first_stage(ok, mask)
+    met = np.zeros((F, L), np.float32)
+    if nfail:
+        dec = oracle.sclc_decode if fixed else oracle.scl_decode
+        li, lok, lm, _, _ = dec(N, L, frozen, frames_in[mask], systematic, crc, paths=True)
+        info[mask], ok[mask], met[mask] = li, lok, lm.astype(np.float32)
+        if nfail >= 16 and not noise:
+            assert 0 < int(lok.sum()) < nfail, f"list stage: {int(lok.sum())} of {nfail} pass"
+        if noise:
+            assert not lok.any()
+    for a in (llr, info, ok, met, mask) + ((x8,) if fixed else ()):
+        a.setflags(write=False)  # shared among tests
+    b = SimpleNamespace(llr=llr, x8=x8, frames=frames_in, info=info, ok=ok, metrics=met, mask=mask)
+    _adaptive_cache[key] = b
+    return b
+
+
+def adaptive_edge_cases():
+    """(code, pattern, fixed, systematic) of tests/test_gpu_adaptive_edges.py's pattern matrix:
+    every pattern at (256, L 4) systematic, four of them at every other code, two on the
+    non-systematic (256, L 4) plan (8-bit too: N >= 256), float and 8-bit."""
+    out = []
+    for fixed in (False, True):
+        out += [("n256_l4", pat, fixed, True) for pat in ADAPTIVE_PATTERNS]
+        out += [(code, pat, fixed, True) for code in ADAPTIVE_CODES if code != "n256_l4"
+                for pat in ("none", "all", "g_plus", "full_wave")]
+        out += [("n256_l4", pat, fixed, False) for pat in ("g_plus", "all")]
+    return out
+
+
+def adaptive_case_batch(oracle, code, pattern, fixed, systematic=True, noise=True, F=None):
+    """(frozen, L, crc, batch) of one pattern on one of ADAPTIVE_CODES.  A batch that fails
+    throughout is noise under CRC-32 wherever K holds 32 check bits (noise=False: the pool's
+    failing rows under the code's own detector, repeated as needed)."""
+    N, K, L, crc = ADAPTIVE_CODES[code]
+    fr = oracle.frozen_bits_bb(N, K, 0.0)
+    mask = adaptive_pattern(pattern, L)
+    if F is not None:
+        assert mask.all() or not mask.any()
+        mask = np.resize(mask, F)
+    if pattern == "all" and noise and K >= 32:
+        crc = 32
+    return fr, L, crc, adaptive_batch(oracle, N, fr, L, crc, mask, fixed=fixed, systematic=systematic)
+
+
 KERNELS = ("interp", "rtc")
 
 
