@@ -809,7 +809,8 @@ static int plan_create_impl(pcg_plan** out,
     }
     if (getenv("PCG_RTC_XOPTS")) // extra compiler options for the specialised kernels
         p->dev_overrides |= PCG_DEV_BUILD;
-    if (!fixed && L > 1 && getenv("PCG_RTC_CLASSES")) // the specialised list walk's A/B switch (scl_rtc_source)
+    // the specialised list walk's A/B switches (scl_rtc_source)
+    if (!fixed && L > 1 && (getenv("PCG_RTC_CLASSES") || getenv("PCG_RTC_STREAMS")))
         p->dev_overrides |= PCG_DEV_BUILD;
     if (const char* e = getenv("PCG_RTC_SCL"); e && e[0] == '0') {
         p->rtc_scl = false;

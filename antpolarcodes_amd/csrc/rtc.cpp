@@ -502,6 +502,21 @@ std::string scl_rtc_source(const PlanHost& h, uint32_t lp, uint32_t Sl, uint32_t
     if (const char* e = getenv("PCG_RTC_CLASSES"))
         classes = e[0] == '0' ? 0u : 1u;
     def("CLASSES", classes);
+    // PCG_RTC_STREAMS=lit[,fgf7[,fgf8[,fg[,leaf]]]] in the environment: dev override of the per-class walk's
+    // literal streaming forms and their batch depths (sclls_kernel.hip, PCG_LS_LIT and PCG_LIT_*), for A/B runs
+    // of one tree; 0 is the parent's walk
+    if (const char* e = getenv("PCG_RTC_STREAMS")) {
+        static const char* const knobs[] = {"PCG_LS_LIT", "PCG_LIT_FGF_U7", "PCG_LIT_FGF_U8", "PCG_LIT_FG_U",
+                                            "PCG_LIT_LEAF_U"};
+        for (int k = 0; k < 5 && *e; ++k) {
+            char* end = nullptr;
+            const unsigned long v = strtoul(e, &end, 10);
+            if (end == e)
+                break;
+            s += std::string("#undef ") + knobs[k] + "\n#define " + knobs[k] + " " + std::to_string(v) + "\n";
+            e = *end == ',' ? end + 1 : end;
+        }
+    }
     s += "#define PCG_RTC_OPS";
     for (size_t k = 0; k < h.ops.size(); ++k)
         s += (k ? "," : " ") + std::to_string(h.ops[k]) + "u";

@@ -503,6 +503,78 @@ PCG_DEV void stream(const Src& src, uint32_t nq, uint32_t sl, Fn&& fn)
     }
 }
 
+// ---- literal chunk counts (the per-class walk, PCG_LS_CLASSES) ---------------------------
+// In the per-class walk the stage is a literal of the instantiation, so whenever every lane
+// works on its own path (Share::shr false: always once P = LP) the chunk count of stream,
+// ls_fg and ls_fgf is a literal too.  Their literal forms (stream_lit, ls_fg_lit, ls_fgf_lit)
+// peel the last ping-pong round instead of wrapping its prefetch to chunk 0: no load without
+// a use (the wrapped batch was still outstanding at the op's end, and the next op's first
+// counted wait drained it), the same loads, arithmetic and stores per element otherwise.
+// The shared form (P < LP) keeps the run-time helpers.  PCG_LS_LIT, bits: 1 ls_fg, 2 ls_fgf,
+// 4 the leaves' stream from the slab; 0: the run-time helpers everywhere (the A/B partner).
+// Only ls_fgf's is on.  (Measured, DESIGN.md: the literal ls_fg costs SCL-8 1.7 %; with the
+// leaves' lambdas inlined four times per stream -- loop and peeled pair -- config 3's kernel
+// goes from 222 VGPRs to 256 with 201 spilled, whether the loop is kept rolled or not.)
+// The batch depths of the literal forms reading the global slab are per-class choices paid
+// from the registers the per-class walk left free (222 of 256):
+//   PCG_LIT_FGF_U7 / _U8  ls_fgf from the slab at stage 7 / stages >= 8 (run-time form: PCG_FGF_U)
+//   PCG_LIT_FG_U          ls_fg from the slab at stages >= 7 (stage 6 is one batch pair already)
+//   PCG_LIT_LEAF_U        the leaves' stream from the slab (Rate-0, Rate-1, SPC at stages >= 6)
+#ifndef PCG_LS_LIT
+#define PCG_LS_LIT 2
+#endif
+#ifndef PCG_LIT_FGF_U7
+#define PCG_LIT_FGF_U7 4
+#endif
+#ifndef PCG_LIT_FGF_U8
+#define PCG_LIT_FGF_U8 4
+#endif
+#ifndef PCG_LIT_FG_U
+#define PCG_LIT_FG_U 4
+#endif
+#ifndef PCG_LIT_LEAF_U
+#define PCG_LIT_LEAF_U 4
+#endif
+// A storage whose node has the literal chunk count NQ, streamed UU chunks per batch.
+template <typename S, uint32_t NQ, int UU>
+struct LitSt {
+    S s;
+    PCG_DEV float4 ld(uint32_t c, uint32_t l) const { return s.ld(c, l); }
+};
+template <typename S, uint32_t NQ, int UU>
+struct Pre<LitSt<S, NQ, UU>> {
+    static constexpr int U = UU;
+};
+// stream over all NQ chunks (NQ and U powers of two): whole batches, the last pair peeled
+template <int U, uint32_t NQ, typename Src, typename Fn>
+PCG_DEV void stream_lit(const Src& src, uint32_t sl, Fn&& fn)
+{
+    float4 xa[U], xb[U];
+    if constexpr (NQ <= (uint32_t)U) {
+        ld_batch<U>(src, 0, NQ, sl, xa);
+        fn(xa, 0u, NQ);
+    } else {
+        ld_full<U>(src, 0, sl, xa);
+        uint32_t c0 = 0;
+#pragma nounroll // (keep the ping-pong order of the batches)
+        for (; c0 + 2 * U < NQ; c0 += 2 * U) {
+            ld_full<U>(src, c0 + U, sl, xb);
+            fn(xa, c0, (uint32_t)U);
+            ld_full<U>(src, c0 + 2 * U, sl, xa);
+            fn(xb, c0 + U, (uint32_t)U);
+        }
+        ld_full<U>(src, c0 + U, sl, xb);
+        fn(xa, c0, (uint32_t)U);
+        fn(xb, c0 + U, (uint32_t)U);
+    }
+}
+template <int U, typename S, uint32_t NQ, int UU, typename Fn>
+PCG_DEV void stream(const LitSt<S, NQ, UU>& src, uint32_t, uint32_t sl, Fn&& fn)
+{
+    static_assert(U == UU, "a literal storage streams at its own depth");
+    stream_lit<U, NQ>(src.s, sl, fn);
+}
+
 // ---- F / G ---------------------------------------------------------------------------
 // Lanes working on one path's F/G.  While fewer than LP paths exist (the start of every
 // codeword: P = 1 until the first branching leaf), lanes p == path (mod P') with
@@ -622,6 +694,82 @@ PCG_DEV void ls_fg(Src src, Dst dst, const DBits& lb, uint32_t s, const Share& w
         body(a1, b1, c0 + U, (uint32_t)U);
     }
 }
+// ls_fg at the literal stage S with every lane on its own path (w.shr false: all 2^(S-4)
+// chunk pairs by this lane), U chunks per batch, the last batch pair peeled.
+template <int OPC, int LP, uint32_t S, int U, typename Src, typename Dst>
+PCG_DEV void ls_fg_lit(Src src, Dst dst, const DBits& lb, const Share& w)
+{
+    constexpr uint32_t hq = 1u << (S - 3);
+    static_assert(U <= 4 || hq % (uint32_t)U == 0u, "a batch of more than 16 elements shares no bit word");
+    const uint32_t sl = w.sl;
+    if (!w.act)
+        return;
+    const Off<Src> sa{ src, 0u }, sb{ src, hq };
+    auto body = [&](const float4 (&xa)[U], const float4 (&xb)[U], uint32_t c0, uint32_t valid) {
+        uint32_t wb[(U + 3) / 4] = {};
+        if (OPC == OP_G) { // 16 elements from a 16-aligned start share a bit word
+#pragma unroll
+            for (int g = 0; g < (U + 3) / 4; ++g)
+                wb[g] = lb.at(4u * (c0 + 4u * g));
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if ((uint32_t)u < valid) {
+                const float4 r = OPC == OP_F ? f4_f(xa[u], xb[u]) : f4_g(xa[u], xb[u], wb[u / 4], 4 * (u % 4));
+                dst.st(c0 + u, r);
+            }
+        }
+    };
+    float4 a0[U], b0[U], a1[U], b1[U];
+    if constexpr (hq <= (uint32_t)U) {
+        ld_batch<U>(sa, 0, hq, sl, a0);
+        ld_batch<U>(sb, 0, hq, sl, b0);
+        body(a0, b0, 0u, hq);
+    } else {
+        ld_full<U>(sa, 0, sl, a0);
+        ld_full<U>(sb, 0, sl, b0);
+        uint32_t c0 = 0;
+#pragma nounroll // (keep the ping-pong order of the batches)
+        for (; c0 + 2 * U < hq; c0 += 2 * U) {
+            ld_full<U>(sa, c0 + U, sl, a1);
+            ld_full<U>(sb, c0 + U, sl, b1);
+            body(a0, b0, c0, (uint32_t)U);
+            ld_full<U>(sa, c0 + 2 * U, sl, a0);
+            ld_full<U>(sb, c0 + 2 * U, sl, b0);
+            body(a1, b1, c0 + U, (uint32_t)U);
+        }
+        ld_full<U>(sa, c0 + U, sl, a1);
+        ld_full<U>(sb, c0 + U, sl, b1);
+        body(a0, b0, c0, (uint32_t)U);
+        body(a1, b1, c0 + U, (uint32_t)U);
+    }
+}
+// batch depth of ls_fg_lit for a storage at stage S
+template <typename S>
+struct IsSlab {
+    enum { v = 0 };
+};
+template <>
+struct IsSlab<GlSt> {
+    enum { v = 1 };
+};
+template <typename Src, uint32_t S>
+constexpr int ls_fg_depth()
+{
+    return IsSlab<Src>::v && S >= 7u ? PCG_LIT_FG_U : Pre<Src>::U;
+}
+// ls_fg, in its literal form where the stage is one (SLIT != 0) and the lanes do not share
+template <int OPC, int LP, uint32_t SLIT, typename Src, typename Dst>
+PCG_DEV void ls_fg_any(Src src, Dst dst, const DBits& lb, uint32_t s, const Share& w)
+{
+    if constexpr (SLIT >= 4u && (PCG_LS_LIT & 1)) {
+        if (!w.shr) { // (wave-uniform)
+            ls_fg_lit<OPC, LP, SLIT, ls_fg_depth<Src, SLIT>()>(src, dst, lb, w);
+            return;
+        }
+    }
+    ls_fg<OPC, LP>(src, dst, lb, s, w);
+}
 
 template <int OPC, bool FU, int LP>
 PCG_DEV void ls_rootv_op(const Ls<LP>& c, GlSt d1, GlSt d2, const DBits& lb, uint32_t s, uint32_t o, const Share& w,
@@ -634,7 +782,8 @@ PCG_DEV void ls_rootv_op(const Ls<LP>& c, GlSt d1, GlSt d2, const DBits& lb, uin
 template <int LP>
 PCG_DEV uint32_t ls_root_round(const Ls<LP>& c, uint32_t s, uint32_t h, bool fused);
 
-template <int OPC, int LP>
+// (SLIT: the stage as a literal, in the per-class walk; 0: run-time)
+template <int OPC, uint32_t SLIT = 0u, int LP>
 PCG_DEV void ls_fg_op(Ls<LP>& c, uint32_t s, uint32_t o, uint32_t P)
 {
     const uint32_t d = s - 1;
@@ -657,15 +806,15 @@ PCG_DEV void ls_fg_op(Ls<LP>& c, uint32_t s, uint32_t o, uint32_t P)
     auto run = [&](auto dst) {
         dst.lane = w.dl;
         if (s == c.top)
-            ls_fg<OPC, LP>(ChSt{ c.y }, dst, lb, s, w);
+            ls_fg_any<OPC, LP, SLIT>(ChSt{ c.y }, dst, lb, s, w);
         else if (s >= c.mt && o < (c.N >> 1))
-            ls_fg<OPC, LP>(RootSt<true>{ c.y, DBits{}, c.N >> 3 }, dst, lb, s, w);
+            ls_fg_any<OPC, LP, SLIT>(RootSt<true>{ c.y, DBits{}, c.N >> 3 }, dst, lb, s, w);
         else if (s >= c.mt)
-            ls_fg<OPC, LP>(RootSt<false>{ c.y, root_bits(c, w), c.N >> 3 }, dst, lb, s, w);
+            ls_fg_any<OPC, LP, SLIT>(RootSt<false>{ c.y, root_bits(c, w), c.N >> 3 }, dst, lb, s, w);
         else if (s >= c.Sl)
-            ls_fg<OPC, LP>(gl_st(c, s), dst, lb, s, w);
+            ls_fg_any<OPC, LP, SLIT>(gl_st(c, s), dst, lb, s, w);
         else
-            ls_fg<OPC, LP>(lds_st(c, s), dst, lb, s, w);
+            ls_fg_any<OPC, LP, SLIT>(lds_st(c, s), dst, lb, s, w);
     };
     if (d >= c.Sl)
         run(gl_st(c, d));
@@ -680,7 +829,7 @@ PCG_DEV void ls_fg_op(Ls<LP>& c, uint32_t s, uint32_t o, uint32_t P)
 // traffic -- disappears.  Chunk c of alpha[s-2] needs alpha[s-1] chunks c and c+hq2,
 // i.e. alpha[s] chunks c, c+hq, c+hq2, c+hq2+hq.  s >= 5, so hq2 >= 2.
 #ifndef PCG_FGF_U
-#define PCG_FGF_U 1 // batch depth of the fused op (VGPR pressure: 2 spills 31 more registers)
+#define PCG_FGF_U 1 // batch depth of the fused op's run-time form (its literal form: PCG_LIT_FGF_U7 / _U8)
 #endif
 template <int OPC, int LP, typename Src, typename Dst1, typename Dst2>
 PCG_DEV void ls_fgf(Src src, Dst1 d1, Dst2 d2, const DBits& lb, uint32_t s, const Share& w)
@@ -727,6 +876,81 @@ PCG_DEV void ls_fgf(Src src, Dst1 d1, Dst2 d2, const DBits& lb, uint32_t s, cons
         load((c0 + 2 * U) & (n - 1), xa);
         body(xb, c0 + U);
     }
+}
+// batch depth of ls_fgf_lit for a storage at stage S (at most the 2^(S-4) output chunks)
+template <typename Src, uint32_t S>
+constexpr int ls_fgf_depth()
+{
+    constexpr int u = IsSlab<Src>::v && S == 7u  ? PCG_LIT_FGF_U7
+                      : IsSlab<Src>::v && S > 7u ? PCG_LIT_FGF_U8
+                      : Pre<Src>::U >= 4         ? PCG_FGF_U
+                                                 : 1;
+    return u < (1 << (S - 4)) ? u : (1 << (S - 4));
+}
+// ls_fgf at the literal stage S with every lane on its own path (w.shr false), U output
+// chunks (4U source chunks) per batch, the last batch pair peeled.
+template <int OPC, int LP, uint32_t S, int U, typename Src, typename Dst1, typename Dst2>
+PCG_DEV void ls_fgf_lit(Src src, Dst1 d1, Dst2 d2, const DBits& lb, const Share& w)
+{
+    constexpr uint32_t hq = 1u << (S - 3), hq2 = hq >> 1, n = hq2;
+    static_assert(U <= 8 && n % (uint32_t)U == 0u, "a batch's 4U elements share a bit word");
+    const uint32_t sl = w.sl;
+    if (!w.act)
+        return;
+    auto load = [&](uint32_t c0, float4 (&x)[4][U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            x[0][u] = src.ld(c0 + u, sl);
+            x[1][u] = src.ld(c0 + hq + u, sl);
+            x[2][u] = src.ld(c0 + hq2 + u, sl);
+            x[3][u] = src.ld(c0 + hq2 + hq + u, sl);
+        }
+    };
+    auto body = [&](const float4 (&x)[4][U], uint32_t c0) {
+        uint32_t wa = 0, wb = 0;
+        if (OPC == OP_G) { // 4U <= 32 elements from a 4U-aligned start share a bit word
+            const uint32_t ia = 4u * c0, ib = ia + 4u * hq2;
+            wa = lb.at(ia);
+            wb = lb.at(ib);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float4 y0 = OPC == OP_F ? f4_f(x[0][u], x[1][u]) : f4_g(x[0][u], x[1][u], wa, 4 * u);
+            const float4 y1 = OPC == OP_F ? f4_f(x[2][u], x[3][u]) : f4_g(x[2][u], x[3][u], wb, 4 * u);
+            d1.st(c0 + u, y0);
+            d1.st(c0 + hq2 + u, y1);
+            d2.st(c0 + u, f4_f(y0, y1));
+        }
+    };
+    float4 xa[4][U], xb[4][U];
+    load(0, xa);
+    if constexpr (n <= (uint32_t)U) {
+        body(xa, 0u);
+    } else {
+        uint32_t c0 = 0;
+#pragma nounroll // (keep the ping-pong order of the batches)
+        for (; c0 + 2 * U < n; c0 += 2 * U) {
+            load(c0 + U, xb);
+            body(xa, c0);
+            load(c0 + 2 * U, xa);
+            body(xb, c0 + U);
+        }
+        load(c0 + U, xb);
+        body(xa, c0);
+        body(xb, c0 + U);
+    }
+}
+// ls_fgf, in its literal form where the stage is one (SLIT != 0) and the lanes do not share
+template <int OPC, int LP, uint32_t SLIT, typename Src, typename Dst1, typename Dst2>
+PCG_DEV void ls_fgf_any(Src src, Dst1 d1, Dst2 d2, const DBits& lb, uint32_t s, const Share& w)
+{
+    if constexpr (SLIT >= 5u && (PCG_LS_LIT & 2)) {
+        if (!w.shr) { // (wave-uniform)
+            ls_fgf_lit<OPC, LP, SLIT, ls_fgf_depth<Src, SLIT>()>(src, d1, d2, lb, w);
+            return;
+        }
+    }
+    ls_fgf<OPC, LP>(src, d1, d2, lb, s, w);
 }
 
 // Fused root-child op (s = top-1: alpha[s] recomputed from the channel) with the channel
@@ -1271,7 +1495,7 @@ PCG_DEV void ls_rootv_op(const Ls<LP>& c, GlSt d1, GlSt d2, const DBits& lb, uin
     }
 }
 
-template <int OPC, int LP>
+template <int OPC, uint32_t SLIT = 0u, int LP>
 PCG_DEV void ls_fgf_op(Ls<LP>& c, uint32_t s, uint32_t o, uint32_t P)
 {
     const uint32_t d = s - 1, e = s - 2;
@@ -1298,17 +1522,17 @@ PCG_DEV void ls_fgf_op(Ls<LP>& c, uint32_t s, uint32_t o, uint32_t P)
         d1.lane = w.dl;
         dst2.lane = w.dl;
         if (s == c.top) {
-            ls_fgf<OPC, LP>(ChSt{ c.y }, d1, dst2, lb, s, w);
+            ls_fgf_any<OPC, LP, SLIT>(ChSt{ c.y }, d1, dst2, lb, s, w);
         } else if (rm && left)
             ls_fgf_root<OPC, true, LP>(c, d1, dst2, lb, rb, s, w, rm);
         else if (rm)
             ls_fgf_root<OPC, false, LP>(c, d1, dst2, lb, rb, s, w, rm);
         else if (rootc && left)
-            ls_fgf<OPC, LP>(RootSt<true>{ c.y, rb, c.N >> 3 }, d1, dst2, lb, s, w);
+            ls_fgf_any<OPC, LP, SLIT>(RootSt<true>{ c.y, rb, c.N >> 3 }, d1, dst2, lb, s, w);
         else if (rootc)
-            ls_fgf<OPC, LP>(RootSt<false>{ c.y, rb, c.N >> 3 }, d1, dst2, lb, s, w);
+            ls_fgf_any<OPC, LP, SLIT>(RootSt<false>{ c.y, rb, c.N >> 3 }, d1, dst2, lb, s, w);
         else
-            ls_fgf<OPC, LP>(gl_st(c, s), d1, dst2, lb, s, w);
+            ls_fgf_any<OPC, LP, SLIT>(gl_st(c, s), d1, dst2, lb, s, w);
     };
     if (e >= c.Sl)
         run(gl_st(c, e));
@@ -2986,7 +3210,10 @@ PCG_DEV void with_stage_lit(const Ls<LP>& c, uint32_t o, Fn&& fn)
     } else if constexpr (S >= rtc_mt) {
         fn(VirtSt<LP>{ &c, c.N >> 3, S != top, o < (c.N >> 1) });
     } else if constexpr (S >= Sl) {
-        fn(gl_st(c, S));
+        if constexpr (PCG_LS_LIT & 4) // the whole node's chunks, PCG_LIT_LEAF_U per batch (stream_lit)
+            fn(LitSt<GlSt, (1u << (S - 2)), PCG_LIT_LEAF_U>{ gl_st(c, S) });
+        else
+            fn(gl_st(c, S));
     } else {
         fn(lds_st(c, S));
     }
@@ -3001,13 +3228,13 @@ PCG_DEV void ls_op_lit(Ls<LP>& c, uint32_t o, uint32_t& P, uint32_t desc)
 {
     [[maybe_unused]] const bool act = c.p < P;
     if constexpr (CODE == OP_F && FUSE)
-        ls_fgf_op<OP_F>(c, S, o, P);
+        ls_fgf_op<OP_F, S>(c, S, o, P);
     else if constexpr (CODE == OP_F)
-        ls_fg_op<OP_F>(c, S, o, P);
+        ls_fg_op<OP_F, S>(c, S, o, P);
     else if constexpr (CODE == OP_G && FUSE)
-        ls_fgf_op<OP_G>(c, S, o, P);
+        ls_fgf_op<OP_G, S>(c, S, o, P);
     else if constexpr (CODE == OP_G)
-        ls_fg_op<OP_G>(c, S, o, P);
+        ls_fg_op<OP_G, S>(c, S, o, P);
     else if constexpr (CODE == OP_COMB)
         ls_comb(c, S, o, act);
     else if constexpr (CODE == OP_S_ST8)
@@ -3439,6 +3666,11 @@ std::string sclls_rtc_defines(bool* nondefault)
     };
     d("PCG_LS_DBITS_LP", PCG_LS_DBITS_LP, 16);
     d("PCG_FGF_U", PCG_FGF_U, 1);
+    d("PCG_LS_LIT", PCG_LS_LIT, 2);
+    d("PCG_LIT_FGF_U7", PCG_LIT_FGF_U7, 4);
+    d("PCG_LIT_FGF_U8", PCG_LIT_FGF_U8, 4);
+    d("PCG_LIT_FG_U", PCG_LIT_FG_U, 4);
+    d("PCG_LIT_LEAF_U", PCG_LIT_LEAF_U, 4);
     d("PCG_STG_GM", PCG_STG_GM, 1);
     d("PCG_STG_DB", PCG_STG_DB, 1);
     d("PCG_DEEP_SHARE", PCG_DEEP_SHARE, 1);

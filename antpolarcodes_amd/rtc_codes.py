@@ -141,6 +141,35 @@ def class_codes():
     ]
 
 
+def stream_codes():
+    """(N, L, frozen spec, crc, systematic): the list codes of tests/test_gpu_rtc_streams.py, the
+    smallest with stages in the global slab under the recomputed top ones (N = 512 and 1024), list
+    sizes 2, 4 and 8.  A random frozen set has its first information bit within the first few
+    positions, so the list is full almost from the start and the per-class walk's literal streaming
+    forms (every lane on its own path) run the ops of stages 6 and 7; the Bhattacharyya sets of
+    rate 1/2 have it late (position 127 of 512, 255 of 1024), so the first F / G ops of those stages run
+    with one path, the lanes sharing its chunks (the run-time forms).  Four codes are new to the
+    catalogue, the others are class_codes', random_list_codes' and config 3."""
+    g = _xorshift(0x5C1A13)
+    pos = list(range(512))
+    nf = 512 // 4 + next(g) % (512 // 2)
+    for i in range(511, 0, -1):
+        j = next(g) % (i + 1)
+        pos[i], pos[j] = pos[j], pos[i]
+    rnd512b = tuple(sorted(pos[:nf]))
+    rnd = {(N, L): tuple(fr) for N, L, fr in random_list_codes()}
+    return [
+        (512, 2, ("BB", 256), 8, True),              # new
+        (512, 4, ("set", rnd512b), 0, True),         # new
+        (512, 8, ("BB", 256), 8, True),              # new
+        (512, 8, ("set", rnd[(512, 8)]), 0, True),
+        (1024, 2, ("BB", 512), 8, True),             # new
+        (1024, 4, ("set", rnd[(1024, 4)]), 0, True),
+        (1024, 8, ("set", rnd[(1024, 8)]), 0, True),
+        (1024, 8, ("BB", 512), 8, True),             # config 3
+    ]
+
+
 def validation_codes():
     """The codes the GPU parity tests run through specialised kernels (tests/test_gpu_rtc.py,
     tests/test_gpu_char.py and the specialised variants of the full-size parity tests)."""
@@ -158,6 +187,7 @@ def validation_codes():
     for N, L, fr in random_list_codes():                  # list plans on random frozen sets
         out.append((N, L, ("set", tuple(fr)), 0, True))
     out += class_codes()                                  # the specialised walk's op classes
+    out += stream_codes()                                 # its literal streaming forms
     out.append((1024, 8, ("5G", 512), 0, True))           # config 4's decoder core with the Dummy detector
     out.append((1024, 1, ("5G", 512), 11, True))          # config 4 through Fast-SSC
     for crc in (8, 16, 32):                               # AdaptiveFloat: both stages
