@@ -50,7 +50,7 @@ struct pcg_plan {
     uint32_t wave_lds_floats = 0;
     uint32_t lds_stage_limit = 0;
     uint32_t scl_virt = 0;
-    uint32_t scl_fuse = 7;
+    uint32_t scl_fuse = 15;       // (KernelArgs::scl_fuse)
     uint32_t scl_lp = 0;          // lane-serial SCL: lanes per codeword (0 = list_pow2(L))
     uint32_t scl_v3 = 0;          // lane-serial SCL: stage 3 recomputed from stage 4 (sclls_layout)
     uint32_t scl_sb = 0;          // lane-serial SCL: bit buffers below this stage in LDS (0: codeword rows)
@@ -784,6 +784,12 @@ static int plan_create_impl(pcg_plan** out,
             p->scl_lp = scl_lp;
         if (const char* e = getenv("PCG_SCL_FUSE")) {
             p->scl_fuse = (uint32_t)atoi(e);
+            p->dev_overrides |= PCG_DEV_SCL_FUSE;
+        }
+        // PCG_SCL_LEFT_ONCE=0/1: the root's left child staged once per codeword (scl_fuse bit 3) or
+        // fetched from the channel by every staged op, for A/B runs of one tree
+        if (const char* e = getenv("PCG_SCL_LEFT_ONCE")) {
+            p->scl_fuse = e[0] == '0' ? p->scl_fuse & ~8u : p->scl_fuse | 8u;
             p->dev_overrides |= PCG_DEV_SCL_FUSE;
         }
         // (an adaptive plan's list stage is one walk over a few frames: its latency, not its

@@ -89,6 +89,21 @@ constexpr __host__ __device__ inline uint64_t ls_gl_alpha_floats(uint32_t mt, ui
     return Sl < mt ? 64ull * ((1ull << mt) - (1ull << Sl)) : 0ull;
 }
 
+// The root's left child F(y_j, y_j+N/2) does not depend on the path: with the quarters (or
+// eighths) recomputed, the first staged op of a codeword -- the stage-(top-V) F at offset 0 --
+// stores it once per codeword, and the later staged ops of the left half fetch it instead of
+// the channel (ls_fgf_rootv: half the chunks, half the rounds).  One image per codeword of the
+// wave, N/8 chunks each, chunk a of codeword g at a * G + g (codeword-minor: the G codewords'
+// chunk a is G * 16 contiguous bytes for the store and for the DMA read), after the D region.
+// Compile-time knob: the region and the code; KernelArgs::scl_fuse bit 3 turns it on per plan.
+#ifndef PCG_STG_LEFT_ONCE
+#define PCG_STG_LEFT_ONCE 1
+#endif
+constexpr __host__ __device__ inline uint64_t ls_left_floats(uint32_t top, uint32_t mt, uint32_t lp)
+{
+    return PCG_STG_LEFT_ONCE && mt > 3u && mt + 2u <= top ? (uint64_t)(64u / lp) << (top - 1u) : 0ull;
+}
+
 // The lowest stages are never stored either (vlow = 1: stage 3, N >= 64; vlow = 2: stages
 // 3 and 4): every reader -- size-8 subtrees, size-8 / size-16 leaves -- recomputes its
 // LLRs from the parent's chunks (F for a left child, G with the left sibling's bits for a
@@ -135,7 +150,9 @@ struct Ls {
     uint32_t lane, p, gb; // lane, path index in the group, group base lane
     uint32_t share;       // idle lanes help with F/G while P < LP (KernelArgs::scl_fuse bit 1)
     uint32_t stage_root;  // root-child ops stage the channel in LDS (KernelArgs::scl_fuse bit 2)
-    uint32_t vlow;        // stages 3 .. 2+vlow recomputed where read (KernelArgs::scl_v3)
+    uint32_t left_once;   // the root's left child staged once per codeword (KernelArgs::scl_fuse bit 3)
+    float* img;           // this wave's left-child images (ls_left_floats)
+    uint32_t vlow;       // stages 3 .. 2+vlow recomputed where read (KernelArgs::scl_v3)
     uint32_t ab;          // ls_abase(vlow)
     uint32_t Sb;          // D stages [4, Sb) in LDS (KernelArgs::scl_sb)
     lds_u32* dl;          // LDS D region: word w of lane l at [(w << 6) + l]
@@ -1230,15 +1247,29 @@ constexpr uint32_t rm_lead_f()
     return l;
 }
 
-template <int OPC, int V, int RM, bool FU, int LP>
+// The root's left child once per codeword (PCG_STG_LEFT_ONCE, c.left_once).  IMG = 1, the writer
+// (the F at offset 0, the codeword's first staged op): after its shared level 1 the whole wave
+// stores that level's chunks -- the left child -- into the wave's image (c.img), one 16-byte
+// store per lane and chunk.  IMG = 2, a reader (every later op of the left half, RM bit 0
+// clear): the image is its source, so the op is the one of a tree one level lower -- VE = V-1
+// levels, RME = RM >> 1, J/2 chunks per source, twice the output chunks per round.  IMG = 0:
+// the channel.
+template <int OPC, int V, int RM, bool FU, int IMG, int LP>
 PCG_DEV void ls_fgf_rootv(const Ls<LP>& c, GlSt d1, GlSt d2, const DBits& lb, const DBits (&vb)[3], uint32_t s,
                           const Share& w, uint32_t m)
 {
-    constexpr uint32_t KS = FU ? 4u : 2u, J = 1u << V;
-    constexpr uint32_t L0 = rm_lead_f<V, RM>(), J0 = J >> L0; // shared levels, chunks left per source
+    static_assert(IMG == 0 || (RM & 1) == 0, "only the left half has an image");
+    static_assert(IMG != 1 || (RM == 0 && OPC == OP_F && PCG_STG_SHARED_F), "the writer is the F at offset 0");
+    constexpr uint32_t LO = IMG == 2 ? 1u : 0u;     // levels the source already holds
+    constexpr uint32_t VE = V - LO, RME = (uint32_t)RM >> LO;
+    constexpr uint32_t KS = FU ? 4u : 2u, J = 1u << VE;
+    constexpr uint32_t L0 = rm_lead_f<VE, RME>(), J0 = J >> L0; // shared levels, chunks left per source
+    constexpr uint32_t G = 64u / LP;
     const uint32_t hq = 1u << (s - 3), hq2 = hq >> 1;
-    const uint32_t hl[3] = { c.N >> 3, c.N >> 4, c.N >> 5 };
+    const uint32_t hl[3] = { c.N >> (3 + LO), c.N >> (4 + LO), c.N >> (5 + LO) }; // (level l of the VE: hl[l-1])
     const uint32_t nout = FU ? hq2 : hq;           // output chunks of the op
+    if (IMG == 2 && 2u * m <= nout)
+        m <<= 1;
     float* stg = c.lds + c.ly.alpha;
     // (wave-uniform) a ring of NB buffers of m/2 output chunks each -- as many as the LDS stage
     // region holds, at most 4 -- when a buffer still gives every lane an output chunk: NB-1 rounds'
@@ -1284,16 +1315,16 @@ PCG_DEV void ls_fgf_rootv(const Ls<LP>& c, GlSt d1, GlSt d2, const DBits& lb, co
         for (uint32_t k = 0; k < KS; ++k) {
             const uint32_t a = cg + koff(k);
 #pragma unroll
-            for (int l = 1; l <= V; ++l) {
-                if (!((RM >> (l - 1)) & 1))
+            for (int l = 1; l <= (int)VE; ++l) {
+                if (!((RME >> (l - 1)) & 1))
                     continue;
 #pragma unroll
                 for (uint32_t i = 0; i < (J >> l); ++i) {
                     uint32_t off = 0;
 #pragma unroll
-                    for (int q = l + 1; q <= V; ++q)
+                    for (int q = l + 1; q <= (int)VE; ++q)
                         off += ((i >> (q - l - 1)) & 1u) ? hl[q - 1] : 0u;
-                    bw[k][J - (J >> (l - 1)) + i] = vb[l - 1].wat(4u * (a + off));
+                    bw[k][J - (J >> (l - 1)) + i] = vb[l - 1 + LO].wat(4u * (a + off));
                 }
             }
         }
@@ -1308,23 +1339,38 @@ PCG_DEV void ls_fgf_rootv(const Ls<LP>& c, GlSt d1, GlSt d2, const DBits& lb, co
 #if defined(PCG_DEV_ABL_DEEP) && PCG_DEV_ABL_DEEP == 1 // dev ablation (wrong results): no channel DMA
         return;
 #endif
-        for (uint32_t t = 0; t < ninst; ++t) {
+        auto one = [&](uint32_t t) {
             const uint32_t f = t * 64u + c.lane;
             uint32_t g, rem;
             stg_slot<LP>(f, per, g, rem);
             const uint32_t u = rem / (KS * J), k = (rem / J) % KS, j = rem % J;
             uint32_t a = r + u + koff(k);
 #pragma unroll
-            for (int l = 1; l <= V; ++l)
+            for (int l = 1; l <= (int)VE; ++l)
                 a += ((j >> (l - 1)) & 1u) ? hl[l - 1] : 0u;
-            const uint32_t lo = shfl((uint32_t)yp, (int)(g * LP)), hi = shfl((uint32_t)(yp >> 32), (int)(g * LP));
-            const float* src = reinterpret_cast<const float*>((uintptr_t)(((uint64_t)hi << 32) | lo)) + 4u * a;
+            const float* src;
+            if constexpr (IMG == 2) {
+                src = c.img + 4u * (a * G + g);
+            } else {
+                const uint32_t lo = shfl((uint32_t)yp, (int)(g * LP)), hi = shfl((uint32_t)(yp >> 32), (int)(g * LP));
+                src = reinterpret_cast<const float*>((uintptr_t)(((uint64_t)hi << 32) | lo)) + 4u * a;
+            }
             if (PCG_STG_DB && !Ls<LP>::DB) // (every round explicitly waited for: s_waitcnt / wait_vm below)
                 glds16(src, stg + hb + t * 256u);
             else {
                 LS_GB(16, 0);
                 __builtin_amdgcn_global_load_lds(src, stg + hb + t * 256u, 16, 0, 0);
             }
+        };
+        if constexpr (IMG == 2) {
+            // (kept rolled: without the channel pointers' shuffles the compiler unrolls this loop and
+            // keeps every address live -- config 3: 256 VGPRs and 12 B of scratch instead of 245 / 0)
+#pragma unroll 1
+            for (uint32_t t = 0; t < ninst; ++t)
+                one(t);
+        } else {
+            for (uint32_t t = 0; t < ninst; ++t)
+                one(t);
         }
     };
     // round k lives in buffer k % NB; the first NB-1 rounds are fetched up front
@@ -1355,7 +1401,9 @@ PCG_DEV void ls_fgf_rootv(const Ls<LP>& c, GlSt d1, GlSt d2, const DBits& lb, co
             }
             // younger than round k's fetch: the fetches of the rounds ahead, and the stores of the
             // rounds computed since it was issued (n outputs x 3 / 1 wave-level stores each)
-            const uint32_t st = n * (FU ? 3u : 1u);
+            // (and, in the writer, the image stores of those rounds: J/2 per trip of the shared-level
+            // loop, whose trips the wave's first lane all takes)
+            const uint32_t st = n * (FU ? 3u : 1u) + (IMG == 1 ? ((G * KS * m + 63u) / 64u) * (J >> 1) : 0u);
             wait_vm(ninst * ahead + st * (k < NB - 1 ? k : NB - 1));
         } else {
             __builtin_amdgcn_s_waitcnt(0);
@@ -1375,10 +1423,25 @@ PCG_DEV void ls_fgf_rootv(const Ls<LP>& c, GlSt d1, GlSt d2, const DBits& lb, co
                 for (uint32_t j = 0; j < J; ++j)
                     v[j] = curw[stg_idx<LP>(q * J + j, g, per)];
 #pragma unroll
-                for (uint32_t l = 1; l <= L0; ++l)
+                for (uint32_t l = 1; l <= L0; ++l) {
 #pragma unroll
                     for (uint32_t i = 0; i < (J >> l); ++i)
                         v[i] = f4_f(v[2 * i], v[2 * i + 1]);
+                    if constexpr (IMG == 1) {
+                        if (l == 1u) { // the left child's chunks a + off(i) of codeword g
+                            const uint32_t a = r + q / KS + koff(q % KS);
+#pragma unroll
+                            for (uint32_t i = 0; i < (J >> 1); ++i) {
+                                uint32_t off = 0;
+#pragma unroll
+                                for (uint32_t b = 0; b + 1u < (uint32_t)V; ++b)
+                                    off += ((i >> b) & 1u) ? hl[b + 1] : 0u;
+                                LS_GB(16, 1);
+                                *reinterpret_cast<float4*>(c.img + 4u * ((a + off) * G + g)) = v[i];
+                            }
+                        }
+                    }
+                }
 #pragma unroll
                 for (uint32_t j = 0; j < J0; ++j)
                     curw[stg_idx<LP>(q * J + j, g, per)] = v[j];
@@ -1412,10 +1475,10 @@ PCG_DEV void ls_fgf_rootv(const Ls<LP>& c, GlSt d1, GlSt d2, const DBits& lb, co
                 for (uint32_t j = 0; j < J0; ++j)
                     v[j] = cur[stg_idx<LP>((u * KS + k) * J + j, mg, per)];
 #pragma unroll
-                for (uint32_t l = L0 + 1; l <= (uint32_t)V; ++l)
+                for (uint32_t l = L0 + 1; l <= VE; ++l)
 #pragma unroll
                     for (uint32_t i = 0; i < (J >> l); ++i)
-                        v[i] = ((RM >> (l - 1)) & 1) ? f4_g(v[2 * i], v[2 * i + 1], bw[k][J - (J >> (l - 1)) + i], gs)
+                        v[i] = ((RME >> (l - 1)) & 1) ? f4_g(v[2 * i], v[2 * i + 1], bw[k][J - (J >> (l - 1)) + i], gs)
                                                      : f4_f(v[2 * i], v[2 * i + 1]);
                 x[k] = v[0];
             }
@@ -1460,6 +1523,31 @@ PCG_DEV void level_bits(const Ls<LP>& c, const Share& w, uint32_t o, DBits (&vb)
             vb[l - 1] = rowbits(c, w.dl, o & ~((1u << st) - 1u));
     }
 }
+// The staged op with its source: the channel, or -- the root's left child staged once per
+// codeword (c.left_once, wave-uniform) -- the writer at the F of offset 0 and the image for the
+// other ops of the left half.  (A reader whose doubled round would not fill one DMA
+// instruction of the wave keeps the channel: a whole small op in one round.)
+template <int OPC, int V, int RM, bool FU, int LP>
+PCG_DEV void ls_rootv_src(const Ls<LP>& c, GlSt d1, GlSt d2, const DBits& lb, const DBits (&vb)[3], uint32_t s,
+                          const Share& w, uint32_t m)
+{
+    if constexpr (PCG_STG_LEFT_ONCE && PCG_STG_SHARED_F && (RM & 1) == 0) {
+        if (c.left_once) {
+            if constexpr (OPC == OP_F && RM == 0) {
+                ls_fgf_rootv<OPC, V, RM, FU, 1, LP>(c, d1, d2, lb, vb, s, w, m);
+                return;
+            } else {
+                const uint32_t nout = FU ? 1u << (s - 4) : 1u << (s - 3);
+                const uint32_t m2 = 2u * m <= nout ? 2u * m : m;
+                if ((64u / LP) * (FU ? 4u : 2u) * (1u << (V - 1)) * m2 >= 64u) {
+                    ls_fgf_rootv<OPC, V, RM, FU, 2, LP>(c, d1, d2, lb, vb, s, w, m);
+                    return;
+                }
+            }
+        }
+    }
+    ls_fgf_rootv<OPC, V, RM, FU, 0, LP>(c, d1, d2, lb, vb, s, w, m);
+}
 // Run the staged op on the recomputed node of stage s = top-V at o (V = 2, or 3 for LP >= 16)
 template <int OPC, bool FU, int LP>
 PCG_DEV void ls_rootv_op(const Ls<LP>& c, GlSt d1, GlSt d2, const DBits& lb, uint32_t s, uint32_t o, const Share& w,
@@ -1474,23 +1562,23 @@ PCG_DEV void ls_rootv_op(const Ls<LP>& c, GlSt d1, GlSt d2, const DBits& lb, uin
         rm |= ((o >> (c.top - l)) & 1u) << (l - 1);
     if (V == 2) {
         switch (rm) {
-        case 0: ls_fgf_rootv<OPC, 2, 0, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
-        case 1: ls_fgf_rootv<OPC, 2, 1, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
-        case 2: ls_fgf_rootv<OPC, 2, 2, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
-        default: ls_fgf_rootv<OPC, 2, 3, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
+        case 0: ls_rootv_src<OPC, 2, 0, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
+        case 1: ls_rootv_src<OPC, 2, 1, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
+        case 2: ls_rootv_src<OPC, 2, 2, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
+        default: ls_rootv_src<OPC, 2, 3, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
         }
         return;
     }
     if constexpr (LP >= 16) {
         switch (rm) {
-        case 0: ls_fgf_rootv<OPC, 3, 0, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
-        case 1: ls_fgf_rootv<OPC, 3, 1, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
-        case 2: ls_fgf_rootv<OPC, 3, 2, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
-        case 3: ls_fgf_rootv<OPC, 3, 3, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
-        case 4: ls_fgf_rootv<OPC, 3, 4, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
-        case 5: ls_fgf_rootv<OPC, 3, 5, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
-        case 6: ls_fgf_rootv<OPC, 3, 6, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
-        default: ls_fgf_rootv<OPC, 3, 7, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
+        case 0: ls_rootv_src<OPC, 3, 0, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
+        case 1: ls_rootv_src<OPC, 3, 1, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
+        case 2: ls_rootv_src<OPC, 3, 2, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
+        case 3: ls_rootv_src<OPC, 3, 3, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
+        case 4: ls_rootv_src<OPC, 3, 4, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
+        case 5: ls_rootv_src<OPC, 3, 5, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
+        case 6: ls_rootv_src<OPC, 3, 6, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
+        default: ls_rootv_src<OPC, 3, 7, FU, LP>(c, d1, d2, lb, vb, s, w, m); break;
         }
     }
 }
@@ -3034,9 +3122,10 @@ PCG_DEV uint32_t crc_syn(const DBits& cw, const uint32_t* rows, uint32_t W, uint
 // ---- punctured frames ------------------------------------------------------------------
 // Scratch floats of one wave without the channel region (alpha slab, tie list, D region);
 // punctured launches append the wave's G depunctured frames (G x N floats) after them.
-constexpr __host__ __device__ inline uint64_t ls_scratch_floats(uint32_t top, uint32_t mt, uint32_t Sl, uint32_t Sb)
+constexpr __host__ __device__ inline uint64_t ls_scratch_floats(uint32_t top, uint32_t mt, uint32_t Sl, uint32_t Sb,
+                                                                uint32_t lp)
 {
-    return ls_gl_alpha_floats(mt, Sl) + 1024ull + 64ull * ls_dgl_words(top, Sb);
+    return ls_gl_alpha_floats(mt, Sl) + 1024ull + 64ull * ls_dgl_words(top, Sb) + ls_left_floats(top, mt, lp);
 }
 // pcg_decode_punctured_f32 on a list plan: the wave's G received frames (E LLRs each) are
 // depunctured into its scratch slab -- position j = llr[pmap[j]] or +0.0 (puncturer.h:92-99:
@@ -3047,7 +3136,7 @@ template <int LP>
 PCG_DEV void ls_depuncture(Ls<LP>& c, const KernelArgs& a, uint64_t frame)
 {
     constexpr uint32_t G = 64 / LP;
-    float* ch = c.gs + ls_scratch_floats(c.top, c.mt, c.Sl, c.Sb);
+    float* ch = c.gs + ls_scratch_floats(c.top, c.mt, c.Sl, c.Sb, LP);
     const uint32_t q = c.N >> 2; // float4 per frame
     for (uint32_t g = 0; g < G; ++g) {
         const uint32_t lo = shfl((uint32_t)frame, (int)(g * LP)), hi = shfl((uint32_t)(frame >> 32), (int)(g * LP));
@@ -3313,6 +3402,8 @@ PCG_DEV void sclls_body(const KernelArgs& a)
     c.gs = a.scratch + (uint64_t)blockIdx.x * a.scratch_floats;
     c.dl = (lds_u32*)(smem + c.ly.d);
     c.dg = (gl_u32*)(c.gs + ls_gl_alpha_floats(c.mt, c.Sl) + 1024u); // after the tie region
+    c.left_once = ls_left_floats(c.top, c.mt, LP) != 0 ? (a.scl_fuse >> 3) & 1u : 0u;
+    c.img = c.gs + (ls_scratch_floats(c.top, c.mt, c.Sl, c.Sb, LP) - ls_left_floats(c.top, c.mt, LP));
     const uint32_t W = a.N >= 32 ? a.N / 32 : 1u;
 
     const uint64_t Fn = a.fcount ? (uint64_t)*a.fcount : a.F;
@@ -3647,7 +3738,7 @@ int sclls_layout(uint32_t N, uint32_t L, uint32_t lp, uint32_t vleaf, uint32_t* 
         return -4;
     *wave_lds_floats = ly.total;
     *lds_stage_limit = Sl;
-    *scratch_floats = ls_scratch_floats(top, mt, Sl, Sb);
+    *scratch_floats = ls_scratch_floats(top, mt, Sl, Sb, lp);
     *virt = vt;
     *v3 = w3;
     *sb = Sb;
@@ -3677,6 +3768,7 @@ std::string sclls_rtc_defines(bool* nondefault)
     d("PCG_F_OLD", PCG_F_OLD, 0);
     d("PCG_SEL_TOP8", PCG_SEL_TOP8, 1);
     d("PCG_STG_SHARED_F", PCG_STG_SHARED_F, 1);
+    d("PCG_STG_LEFT_ONCE", PCG_STG_LEFT_ONCE, 1);
     d("PCG_STG_RING", PCG_STG_RING, 2);
     d("PCG_STG_TAIL_DRAIN", PCG_STG_TAIL_DRAIN, 0);
     d("PCG_LS_STAGGER", PCG_LS_STAGGER, 2);

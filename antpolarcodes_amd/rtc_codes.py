@@ -170,6 +170,23 @@ def stream_codes():
     ]
 
 
+def left_once_codes():
+    """(N, L, frozen spec, crc, systematic): the list codes of tests/test_gpu_left_once.py -- the
+    root's left child staged once per codeword (sclls_kernel.hip, PCG_STG_LEFT_ONCE).  N = 512
+    (quarters stored) and 1024 (quarters recomputed inside their staged ops), list sizes 2, 4 and
+    8; the Bhattacharyya sets of rate 1/2 freeze the first eighth (one path at both ops of the first
+    quarter), the random sets have information bits from the first few
+    positions (a full list at the second quarter); one non-systematic.  Three codes are new to
+    the catalogue, the others are stream_codes'."""
+    rnd = {(N, L): tuple(fr) for N, L, fr in random_list_codes()}
+    old = [c for c in stream_codes() if c[1] in (2, 4, 8)]
+    return old + [
+        (1024, 4, ("BB", 512), 8, True),              # new
+        (1024, 2, ("set", rnd[(1024, 8)]), 0, True),  # new
+        (1024, 8, ("BB", 512), 8, False),             # new
+    ]
+
+
 def validation_codes():
     """The codes the GPU parity tests run through specialised kernels (tests/test_gpu_rtc.py,
     tests/test_gpu_char.py and the specialised variants of the full-size parity tests)."""
@@ -188,6 +205,7 @@ def validation_codes():
         out.append((N, L, ("set", tuple(fr)), 0, True))
     out += class_codes()                                  # the specialised walk's op classes
     out += stream_codes()                                 # its literal streaming forms
+    out += left_once_codes()                              # the left child staged once per codeword
     out.append((1024, 8, ("5G", 512), 0, True))           # config 4's decoder core with the Dummy detector
     out.append((1024, 1, ("5G", 512), 11, True))          # config 4 through Fast-SSC
     for crc in (8, 16, 32):                               # AdaptiveFloat: both stages
