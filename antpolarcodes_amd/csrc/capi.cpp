@@ -676,6 +676,51 @@ int pcg_dev_rtc_classes(const pcg_plan* p, uint32_t* keys, int nkeys, uint32_t* 
     return n;
 }
 
+// Development aid, not part of include/pcg.h: the compacted table the specialised list kernel's
+// per-class walk reads (sclls_kernel.hip ls_compact on ls_classify's output, run here as the
+// kernel source runs it at compile time).  mode: as PCG_RTC_COMPACT, or < 0 for the one the plan's
+// kernel is generated with; info[0] = that mode, info[1] = the first recomputed stage (mt),
+// info[2] = the number of recomputed low stages (vlow), info[3] = the number of dropped words.
+// keys[0 .. *ncls): pcg_dev_rtc_classes' keys, and 0xf0 | first stage << 8 | length << 24 for a run
+// of Combines, 0xf1 | first stage << 8 | fused << 16 | length << 24 for a run and the G of its
+// node's parent.  pos: four words per walk position -- class id | schedule words covered << 8 |
+// offset << 16 (a run: its last node's), the second schedule word consumed (an ST8's descriptor, a
+// fused op's child F) or 0, the index of the first schedule word covered, the kind (0 plain, 1
+// run, 2 run + G).  dropped: the indices of the schedule words left out.  Returns the number of positions; PCG_E_UNSUPPORTED for a plan that is
+// not a float list plan.
+int pcg_dev_rtc_walk(const pcg_plan* p, int mode, uint32_t* keys, int nkeys, int* ncls, uint32_t* pos, int npos,
+                     uint32_t* dropped, int ndropped, uint32_t* info)
+{
+    if (!p || !keys || !pos || !ncls || !dropped || !info || nkeys < 0 || npos < 0 || ndropped < 0)
+        return fail(PCG_E_ARG, "null argument");
+    if (p->host.fixed || p->host.L < 2 || p->soft_plan())
+        return fail(PCG_E_UNSUPPORTED, "walk table: not a float list plan");
+    const auto& ops = p->host.ops;
+    const uint32_t m = mode < 0 ? pcg::rtc_compact_mode(p->scl_lp) : (uint32_t)mode;
+    std::vector<uint32_t> k, q(2 * ops.size() + 2), first(ops.size() + 1), d;
+    const int n = pcg::sclls_rtc_walk(ops.data(), (uint32_t)ops.size(), p->host.log2N, p->lds_stage_limit, p->scl_virt,
+                                      p->scl_v3, p->scl_fuse, m, &k, q.data(), first.data(), &d);
+    if (n < 0)
+        return fail(PCG_E_UNSUPPORTED, "walk table: too many classes");
+    for (int i = 0; i < nkeys && i < (int)k.size(); ++i)
+        keys[i] = k[i];
+    for (int i = 0; i < npos && i < n; ++i) {
+        pos[4 * i] = q[2 * i];
+        pos[4 * i + 1] = q[2 * i + 1];
+        pos[4 * i + 2] = first[i];
+        const uint32_t code = k[q[2 * i] & 0xffu] & 0xffu;
+        pos[4 * i + 3] = code == 0xf0u ? 1u : (code == 0xf1u ? 2u : 0u);
+    }
+    for (int i = 0; i < ndropped && i < (int)d.size(); ++i)
+        dropped[i] = d[i];
+    *ncls = (int)k.size();
+    info[0] = m;
+    info[1] = p->host.log2N > p->scl_virt + 3u ? p->host.log2N - p->scl_virt : 3u;
+    info[2] = p->scl_v3;
+    info[3] = (uint32_t)d.size();
+    return n;
+}
+
 // Development aid, not part of include/pcg.h: hiprtc compiles this process started.
 int pcg_dev_rtc_compiles(void) { return pcg::rtc_compiles(); }
 
@@ -816,7 +861,7 @@ static int plan_create_impl(pcg_plan** out,
     if (getenv("PCG_RTC_XOPTS")) // extra compiler options for the specialised kernels
         p->dev_overrides |= PCG_DEV_BUILD;
     // the specialised list walk's A/B switches (scl_rtc_source)
-    if (!fixed && L > 1 && (getenv("PCG_RTC_CLASSES") || getenv("PCG_RTC_STREAMS")))
+    if (!fixed && L > 1 && (getenv("PCG_RTC_CLASSES") || getenv("PCG_RTC_STREAMS") || getenv("PCG_RTC_COMPACT")))
         p->dev_overrides |= PCG_DEV_BUILD;
     if (const char* e = getenv("PCG_RTC_SCL"); e && e[0] == '0') {
         p->rtc_scl = false;

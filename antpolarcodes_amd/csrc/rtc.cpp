@@ -477,6 +477,14 @@ std::string sclc_rtc_source(const PlanHost& h, uint32_t lp, uint32_t Sl)
     return s;
 }
 
+uint32_t rtc_compact_mode(uint32_t lp)
+{
+    uint32_t m = lp <= 8 ? 1u : 0u;
+    if (const char* e = getenv("PCG_RTC_COMPACT"))
+        m = e[0] == '0' ? 0u : (e[0] == '2' ? 2u : 1u);
+    return m;
+}
+
 std::string scl_rtc_source(const PlanHost& h, uint32_t lp, uint32_t Sl, uint32_t virt, uint32_t v3, uint32_t sb,
                            uint32_t fuse)
 {
@@ -502,6 +510,8 @@ std::string scl_rtc_source(const PlanHost& h, uint32_t lp, uint32_t Sl, uint32_t
     if (const char* e = getenv("PCG_RTC_CLASSES"))
         classes = e[0] == '0' ? 0u : 1u;
     def("CLASSES", classes);
+    // the table that walk reads, compacted (sclls_kernel.hip, ls_compact) or one position per op
+    def("COMPACT", classes ? rtc_compact_mode(lp) : 0u);
     // PCG_RTC_STREAMS=lit[,fgf7[,fgf8[,fg[,leaf]]]] in the environment: dev override of the per-class walk's
     // literal streaming forms and their batch depths (sclls_kernel.hip, PCG_LS_LIT and PCG_LIT_*), for A/B runs
     // of one tree; 0 is the parent's walk

@@ -32,6 +32,21 @@ std::string sclls_rtc_defines(bool* nondefault);
 // many classes.
 int sclls_rtc_classes(const uint32_t* ops, uint32_t nops, uint32_t log2N, uint32_t Sl, uint32_t virt, uint32_t fuse,
                       std::vector<uint32_t>* keys, uint32_t* pos);
+// sclls_kernel.hip (host part): the compacted table the per-class walk reads (ls_compact run on
+// ls_classify's output under the layout's recomputed stages; mode as PCG_RTC_COMPACT).  keys:
+// ls_classify's, 0xf0 | first stage << 8 | length << 24 for a run of Combines and 0xf1 | first
+// stage << 8 | fused << 16 | length << 24 for a run with the G of its node's parent; pos as above
+// (a run: every word it covers in the words consumed, its last node's offset); first[i]: the
+// index of position i's first schedule word; dropped: the indices of the words left out.
+// Returns the positions, -1: too many classes.
+int sclls_rtc_walk(const uint32_t* ops, uint32_t nops, uint32_t log2N, uint32_t Sl, uint32_t virt, uint32_t v3,
+                   uint32_t fuse, uint32_t mode, std::vector<uint32_t>* keys, uint32_t* pos, uint32_t* first,
+                   std::vector<uint32_t>* dropped);
+// The walk table of a list plan's specialised kernel of lp lanes per codeword: 0 one position per
+// op class position, 1 compacted (empty positions left out, Combine runs one position), 2 runs
+// handed to their parent's G as well; PCG_RTC_COMPACT in the environment overrides the default
+// (dev: A/B runs of one tree)
+uint32_t rtc_compact_mode(uint32_t lp);
 
 // One compile of one generated source, shared by every plan (and thread) asking for it.
 struct RtcJob;

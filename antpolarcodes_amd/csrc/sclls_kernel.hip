@@ -275,6 +275,26 @@ PCG_DEV DBits gbits(const Ls<LP>& c, uint32_t s, uint32_t o, uint32_t dl, uint32
         return rowbits(c, dl, o);
 }
 
+// A G's left bits held in registers: the NW row words of its left child, word 0 the one holding
+// the node's first bit (at bit `base`) -- what a Combine run leaves there (ls_comb_run_regs).
+template <uint32_t NW>
+struct RegBits {
+    uint32_t x[NW];
+    uint32_t base;
+    PCG_DEV uint32_t word(uint32_t w) const
+    {
+        uint32_t v = x[0];
+#pragma unroll
+        for (uint32_t k = 1; k < NW; ++k)
+            v = w == k ? x[k] : v;
+        return v;
+    }
+    PCG_DEV uint32_t at(uint32_t i) const { return word((base + i) >> 5) >> ((base + i) & 31u); }
+};
+struct NoHook {
+    PCG_DEV void operator()() const {}
+};
+
 // Stage storages.  ld(c, l): float4 chunk c of lane l's buffer; st(c, v): own lane.
 struct LdsSt {
     float* b;
@@ -667,8 +687,10 @@ struct Pre<Off<S>> {
 // alpha[s-1] of every active path from alpha[s] of its slot (avx_float.h:101-164),
 // h = 2^(s-1) >= 8 elements = hq float4 chunks (a power of two >= 2); the two halves
 // are streamed together, chunks [cb, cb+n) by this lane.
-template <int OPC, int LP, typename Src, typename Dst>
-PCG_DEV void ls_fg(Src src, Dst dst, const DBits& lb, uint32_t s, const Share& w)
+// (Bits: where a G's left bits come from -- DBits, or RegBits with HOOK run once by an active lane
+// after the op's first loads are issued: the Combine run handed to its parent's G, ls_fg_op)
+template <int OPC, int LP, typename Src, typename Dst, typename Bits = DBits, typename Hook = NoHook>
+PCG_DEV void ls_fg(Src src, Dst dst, const Bits& lb, uint32_t s, const Share& w, Hook hook = Hook{})
 {
     constexpr int U = Pre<Src>::U;
     const uint32_t hq = 1u << (s - 3), n = hq / w.h, cb = n * w.i;
@@ -694,6 +716,7 @@ PCG_DEV void ls_fg(Src src, Dst dst, const DBits& lb, uint32_t s, const Share& w
         ld_batch<U>(sb, 0, n, sl, b0);
         ld_batch<U>(sa, U, n, sl, a1);
         ld_batch<U>(sb, U, n, sl, b1);
+        hook();
         body(a0, b0, 0u, n < (uint32_t)U ? n : (uint32_t)U);
         if (n > (uint32_t)U)
             body(a1, b1, (uint32_t)U, n - U);
@@ -701,6 +724,7 @@ PCG_DEV void ls_fg(Src src, Dst dst, const DBits& lb, uint32_t s, const Share& w
     }
     ld_full<U>(sa, 0, sl, a0);
     ld_full<U>(sb, 0, sl, b0);
+    hook();
     for (uint32_t c0 = 0; c0 < n; c0 += 2 * U) {
         ld_full<U>(sa, c0 + U, sl, a1);
         ld_full<U>(sb, c0 + U, sl, b1);
@@ -713,8 +737,8 @@ PCG_DEV void ls_fg(Src src, Dst dst, const DBits& lb, uint32_t s, const Share& w
 }
 // ls_fg at the literal stage S with every lane on its own path (w.shr false: all 2^(S-4)
 // chunk pairs by this lane), U chunks per batch, the last batch pair peeled.
-template <int OPC, int LP, uint32_t S, int U, typename Src, typename Dst>
-PCG_DEV void ls_fg_lit(Src src, Dst dst, const DBits& lb, const Share& w)
+template <int OPC, int LP, uint32_t S, int U, typename Src, typename Dst, typename Bits = DBits, typename Hook = NoHook>
+PCG_DEV void ls_fg_lit(Src src, Dst dst, const Bits& lb, const Share& w, Hook hook = Hook{})
 {
     constexpr uint32_t hq = 1u << (S - 3);
     static_assert(U <= 4 || hq % (uint32_t)U == 0u, "a batch of more than 16 elements shares no bit word");
@@ -741,10 +765,12 @@ PCG_DEV void ls_fg_lit(Src src, Dst dst, const DBits& lb, const Share& w)
     if constexpr (hq <= (uint32_t)U) {
         ld_batch<U>(sa, 0, hq, sl, a0);
         ld_batch<U>(sb, 0, hq, sl, b0);
+        hook();
         body(a0, b0, 0u, hq);
     } else {
         ld_full<U>(sa, 0, sl, a0);
         ld_full<U>(sb, 0, sl, b0);
+        hook();
         uint32_t c0 = 0;
 #pragma nounroll // (keep the ping-pong order of the batches)
         for (; c0 + 2 * U < hq; c0 += 2 * U) {
@@ -776,16 +802,16 @@ constexpr int ls_fg_depth()
     return IsSlab<Src>::v && S >= 7u ? PCG_LIT_FG_U : Pre<Src>::U;
 }
 // ls_fg, in its literal form where the stage is one (SLIT != 0) and the lanes do not share
-template <int OPC, int LP, uint32_t SLIT, typename Src, typename Dst>
-PCG_DEV void ls_fg_any(Src src, Dst dst, const DBits& lb, uint32_t s, const Share& w)
+template <int OPC, int LP, uint32_t SLIT, typename Src, typename Dst, typename Bits = DBits, typename Hook = NoHook>
+PCG_DEV void ls_fg_any(Src src, Dst dst, const Bits& lb, uint32_t s, const Share& w, Hook hook = Hook{})
 {
     if constexpr (SLIT >= 4u && (PCG_LS_LIT & 1)) {
         if (!w.shr) { // (wave-uniform)
-            ls_fg_lit<OPC, LP, SLIT, ls_fg_depth<Src, SLIT>()>(src, dst, lb, w);
+            ls_fg_lit<OPC, LP, SLIT, ls_fg_depth<Src, SLIT>()>(src, dst, lb, w, hook);
             return;
         }
     }
-    ls_fg<OPC, LP>(src, dst, lb, s, w);
+    ls_fg<OPC, LP>(src, dst, lb, s, w, hook);
 }
 
 template <int OPC, bool FU, int LP>
@@ -799,16 +825,51 @@ PCG_DEV void ls_rootv_op(const Ls<LP>& c, GlSt d1, GlSt d2, const DBits& lb, uin
 template <int LP>
 PCG_DEV uint32_t ls_root_round(const Ls<LP>& c, uint32_t s, uint32_t h, bool fused);
 
-// (SLIT: the stage as a literal, in the per-class walk; 0: run-time)
-template <int OPC, uint32_t SLIT = 0u, int LP>
+// An F / G at stage s whose output stage s - 1 is never stored (at or above mt, or one of the
+// vlow lowest): recomputed where it is read, so the op itself does nothing.  (A fused F / G + F
+// never is one: its output stage is in the slab, ls_classify.)  The one statement of the rule:
+// the op returns on it, the compacted walk table leaves the position out (ls_compact).
+constexpr PCG_HD inline bool ls_fg_empty(uint32_t s, uint32_t mt, uint32_t vlow)
+{
+    return s - 1u >= mt || s - 1u < 3u + vlow;
+}
+
+// A Combine run handed to its parent's G (the compacted walk table, ls_compact mode 2): the G
+// at stage s = RS0 + RLEN of the node at o, whose left child the run of RLEN Combines from stage
+// RS0 has just finished (ls_comb_run).  Every lane on its own path: the G's first loads are
+// issued, then the run is done in registers and its row words stored, and the G takes its bits
+// from those registers -- no LDS round trip between the two, and the run's in the shadow of the
+// loads.  Lanes sharing paths (P < LP) do not hold the owner's registers: the run, a wave
+// barrier, then the G reading the row, as two positions would.
+// (row words of the last node of a run of LEN Combines from stage S0)
+constexpr uint32_t ls_run_words(uint32_t S0, uint32_t LEN) { return S0 + LEN - 1u > 5u ? 1u << (S0 + LEN - 6u) : 1u; }
+template <int LP, uint32_t S0, uint32_t LEN, uint32_t NW>
+PCG_DEV void ls_comb_run_regs(const Ls<LP>& c, uint32_t o, uint32_t (&x)[NW]);
+template <int LP, uint32_t S0, uint32_t LEN>
+PCG_DEV void ls_comb_run(Ls<LP>& c, uint32_t o, bool act);
+template <int LP, uint32_t RS0, uint32_t RLEN>
+PCG_DEV void ls_run_first(Ls<LP>& c, uint32_t o, uint32_t P, const Share& w)
+{
+    if constexpr (RLEN != 0u) {
+        if (w.shr) { // (wave-uniform)
+            ls_comb_run<LP, RS0, RLEN>(c, o, c.p < P);
+            wsync();
+        }
+    }
+}
+
+// (SLIT: the stage as a literal, in the per-class walk; 0: run-time.  RS0, RLEN: the Combine run
+// this G also does, see above)
+template <int OPC, uint32_t SLIT = 0u, uint32_t RS0 = 0u, uint32_t RLEN = 0u, int LP>
 PCG_DEV void ls_fg_op(Ls<LP>& c, uint32_t s, uint32_t o, uint32_t P)
 {
     const uint32_t d = s - 1;
-    if (d >= c.mt || d < 3u + c.vlow) // recomputed where it is read
+    if (ls_fg_empty(s, c.mt, c.vlow)) // recomputed where it is read
         return;
     const bool deep = s >= c.mt && s + 2u <= c.top; // a recomputed quarter / eighth
     // (those: at most as many lanes per path as one staging round has output chunks)
     const Share w = ls_share(c, P, s, deep ? PCG_DEEP_SHARE * 2u * ls_root_round(c, s, 1u, false) : 1u << (s - 3));
+    ls_run_first<LP, RS0, RLEN>(c, o, P, w);
     const DBits lb = gbits(c, s, o, w.dl, w.bl);
     if (deep) { // its child is a leaf: staged, unfused (alpha[s-1] is global)
         const uint32_t rm = ls_root_round(c, s, w.h, false);
@@ -822,6 +883,18 @@ PCG_DEV void ls_fg_op(Ls<LP>& c, uint32_t s, uint32_t o, uint32_t P)
     }
     auto run = [&](auto dst) {
         dst.lane = w.dl;
+        if constexpr (RLEN != 0u) { // (a stored source stage: ls_compact)
+            if (!w.shr) {
+                RegBits<ls_run_words(RS0, RLEN)> rb;
+                rb.base = o & 31u;
+                auto hook = [&]() { ls_comb_run_regs<LP, RS0, RLEN>(c, o, rb.x); };
+                if (s >= c.Sl)
+                    ls_fg_any<OPC, LP, SLIT>(gl_st(c, s), dst, rb, s, w, hook);
+                else
+                    ls_fg_any<OPC, LP, SLIT>(lds_st(c, s), dst, rb, s, w, hook);
+                return;
+            }
+        }
         if (s == c.top)
             ls_fg_any<OPC, LP, SLIT>(ChSt{ c.y }, dst, lb, s, w);
         else if (s >= c.mt && o < (c.N >> 1))
@@ -906,8 +979,9 @@ constexpr int ls_fgf_depth()
 }
 // ls_fgf at the literal stage S with every lane on its own path (w.shr false), U output
 // chunks (4U source chunks) per batch, the last batch pair peeled.
-template <int OPC, int LP, uint32_t S, int U, typename Src, typename Dst1, typename Dst2>
-PCG_DEV void ls_fgf_lit(Src src, Dst1 d1, Dst2 d2, const DBits& lb, const Share& w)
+template <int OPC, int LP, uint32_t S, int U, typename Src, typename Dst1, typename Dst2, typename Bits = DBits,
+          typename Hook = NoHook>
+PCG_DEV void ls_fgf_lit(Src src, Dst1 d1, Dst2 d2, const Bits& lb, const Share& w, Hook hook = Hook{})
 {
     constexpr uint32_t hq = 1u << (S - 3), hq2 = hq >> 1, n = hq2;
     static_assert(U <= 8 && n % (uint32_t)U == 0u, "a batch's 4U elements share a bit word");
@@ -941,6 +1015,7 @@ PCG_DEV void ls_fgf_lit(Src src, Dst1 d1, Dst2 d2, const DBits& lb, const Share&
     };
     float4 xa[4][U], xb[4][U];
     load(0, xa);
+    hook();
     if constexpr (n <= (uint32_t)U) {
         body(xa, 0u);
     } else {
@@ -1583,7 +1658,8 @@ PCG_DEV void ls_rootv_op(const Ls<LP>& c, GlSt d1, GlSt d2, const DBits& lb, uin
     }
 }
 
-template <int OPC, uint32_t SLIT = 0u, int LP>
+// (RS0, RLEN: the Combine run this G also does, as ls_fg_op; registers only for the literal form)
+template <int OPC, uint32_t SLIT = 0u, uint32_t RS0 = 0u, uint32_t RLEN = 0u, int LP>
 PCG_DEV void ls_fgf_op(Ls<LP>& c, uint32_t s, uint32_t o, uint32_t P)
 {
     const uint32_t d = s - 1, e = s - 2;
@@ -1591,6 +1667,13 @@ PCG_DEV void ls_fgf_op(Ls<LP>& c, uint32_t s, uint32_t o, uint32_t P)
     // (quarters / eighths: at most as many lanes per path as a staging round has output chunks,
     // so that the idle lanes of a codeword with P < LP paths share its staged rounds)
     const Share w = ls_share(c, P, s, deep ? PCG_DEEP_SHARE * 2u * ls_root_round(c, s, 1u, true) : 1u << (s - 4));
+    constexpr bool RREG = RLEN != 0u && SLIT >= 5u && (PCG_LS_LIT & 2);
+    if constexpr (RLEN != 0u && !RREG) {
+        ls_comb_run<LP, RS0, RLEN>(c, o, c.p < P);
+        wsync();
+    } else {
+        ls_run_first<LP, RS0, RLEN>(c, o, P, w);
+    }
     const DBits lb = gbits(c, s, o, w.dl, w.bl);
     const uint32_t rm = ls_root_round(c, s, w.h, true);
     if (deep) { // a recomputed quarter / eighth: staged (its grandchild alpha[s-2] is global)
@@ -1609,6 +1692,15 @@ PCG_DEV void ls_fgf_op(Ls<LP>& c, uint32_t s, uint32_t o, uint32_t P)
         GlSt d1 = gl_st(c, d);
         d1.lane = w.dl;
         dst2.lane = w.dl;
+        if constexpr (RREG) { // (the source stage in the slab: ls_compact)
+            if (!w.shr) {
+                RegBits<ls_run_words(RS0, RLEN)> rb;
+                rb.base = o & 31u;
+                auto hook = [&]() { ls_comb_run_regs<LP, RS0, RLEN>(c, o, rb.x); };
+                ls_fgf_lit<OPC, LP, SLIT, ls_fgf_depth<GlSt, SLIT>()>(gl_st(c, s), d1, dst2, rb, w, hook);
+                return;
+            }
+        }
         if (s == c.top) {
             ls_fgf_any<OPC, LP, SLIT>(ChSt{ c.y }, d1, dst2, lb, s, w);
         } else if (rm && left)
@@ -1786,6 +1878,59 @@ PCG_DEV void ls_comb(Ls<LP>& c, uint32_t s, uint32_t o, bool act)
         });
     }
     d_end(c, s, o);
+}
+
+// A run of LEN Combines up one node chain (the compacted walk table, ls_compact): stages S0 ..
+// S0 + LEN - 1, each node the right child of the next, so all of them end where the last
+// (largest) one, at o, ends.  In the codeword rows: the last node's NW row words are loaded
+// once, the stages applied in registers in the order of the separate ops -- within the last
+// word (stages <= 5: the node of stage s is its top 2^s bits), then word ^= word (stage s >= 6:
+// the 2^(s-6) words below the node's upper half) -- and the changed words stored once.
+template <uint32_t S, uint32_t SE, uint32_t NW>
+PCG_DEV void comb_run_stages(uint32_t (&x)[NW], uint32_t o)
+{
+    if constexpr (S <= SE) {
+        constexpr uint32_t h = 1u << (S - 1u);
+        if constexpr (S <= 5u) {
+            // (SE <= 5: one word, the node of stage S at o + 2^SE - 2^S)
+            const uint32_t sh = SE <= 5u ? (o + (1u << SE) - (1u << S)) & 31u : (32u - (1u << S)) & 31u;
+            const uint32_t msk = ((1u << h) - 1u) << sh;
+            x[NW - 1u] ^= (x[NW - 1u] >> h) & msk;
+        } else {
+            constexpr uint32_t nw = h >> 5;
+#pragma unroll
+            for (uint32_t i = 0; i < nw; ++i)
+                x[NW - 2u * nw + i] ^= x[NW - nw + i];
+        }
+        comb_run_stages<S + 1u, SE, NW>(x, o);
+    }
+}
+// the run by an active lane; x: the last node's row words as the run leaves them
+template <int LP, uint32_t S0, uint32_t LEN, uint32_t NW>
+PCG_DEV void ls_comb_run_regs(const Ls<LP>& c, uint32_t o, uint32_t (&x)[NW])
+{
+    static_assert(!Ls<LP>::DB && LEN >= 1u && S0 >= 1u, "Combine runs: codeword rows only");
+    static_assert(NW == ls_run_words(S0, LEN), "the last node's words");
+    constexpr uint32_t SE = S0 + LEN - 1u;
+    // words [0, NST) change: all of them when the run has a stage <= 5 (the last word), else
+    // those below the first node's upper half
+    constexpr uint32_t NST = S0 <= 5u ? NW : NW - (1u << (S0 - 6u));
+    lds_u32* w = c.row() + ((o >> 5) << 6);
+#pragma unroll
+    for (uint32_t i = 0; i < NW; ++i)
+        x[i] = w[i << 6];
+    comb_run_stages<S0, SE, NW>(x, o);
+#pragma unroll
+    for (uint32_t i = 0; i < NST; ++i)
+        w[i << 6] = x[i];
+}
+template <int LP, uint32_t S0, uint32_t LEN>
+PCG_DEV void ls_comb_run(Ls<LP>& c, uint32_t o, bool act)
+{
+    if (!act)
+        return;
+    uint32_t x[ls_run_words(S0, LEN)];
+    ls_comb_run_regs<LP, S0, LEN>(c, o, x);
 }
 
 // Rate-0: the all-zero estimate.
@@ -3237,6 +3382,103 @@ constexpr PCG_HD inline uint32_t ls_classify(const uint32_t* ops, uint32_t nops,
     return np;
 }
 
+// ---- the compacted walk table (PCG_RTC_COMPACT) ------------------------------------------
+// A second pass over ls_classify's table; the per-class walk reads its output.  Under the
+// kernel's literal layout (mt, vlow)
+//   * a position whose op is empty (ls_fg_empty: an unfused F / G whose output stage is
+//     recomputed where it is read) is left out: nothing is loaded, dispatched or synchronised
+//     for it;
+//   * a maximal run of consecutive Combines of one node chain -- COMB s at o, then COMB s + 1
+//     at o - 2^s, ... -- becomes one position of the walk-only class LS_WK_RUN (ls_comb_run:
+//     the node's row words loaded once, combined in registers, stored once).  Runs stop at
+//     stage LS_RUN_MAXS (32 row words in registers); a single Combine keeps its class;
+//   * mode 2: a run, of one Combine too, directly followed by the G of the node's parent -- at
+//     the next stage and the run's last offset -- whose source stage is stored (below mt: the
+//     LDS-source G, the slab-source G, the fused slab G + child F; not a recomputed quarter's,
+//     not an empty one) and at most LS_RUNG_MAXS (4 bit words in registers) becomes one position
+//     of the walk-only class LS_WK_RUNG (ls_fg_op / ls_fgf_op with the run's literals).
+// Keys: those of ls_classify, and LS_WK_RUN | first stage << 8 | length << 24 for a run,
+// LS_WK_RUNG | first stage << 8 | the G's fused bit << 16 | length << 24 for a run and its G (at
+// stage first + length).  A position keeps the two-word format (class id | words consumed << 8 |
+// offset << 16, second word: the G's fused child F); a run's offset is its last (largest) node's.
+// first[i] (if given) is the index of position i's first schedule word, drop[0 .. *ndrop) the
+// indices of the words left out.  Returns the positions, ~0u: more than LS_MAXCLS classes.
+constexpr uint32_t LS_WK_RUN = 0xf0u, LS_WK_RUNG = 0xf1u;
+constexpr uint32_t LS_RUN_MAXS = 10u, LS_RUNG_MAXS = 8u;
+constexpr PCG_HD inline uint32_t ls_class_len(uint32_t key) { return key >> 24; }
+constexpr PCG_HD inline uint32_t ls_compact(const uint32_t* keys, uint32_t ncls, const uint32_t* pos, uint32_t npos,
+                                            uint32_t mt, uint32_t vlow, uint32_t mode, uint32_t* ckeys, uint32_t* cncls,
+                                            uint32_t* cpos, uint32_t* first, uint32_t* drop, uint32_t* ndrop)
+{
+    uint32_t nc = 0, np = 0, nd = 0, k = 0;
+    (void)ncls;
+    for (uint32_t i = 0; i < npos; ++i) {
+        const uint32_t e = pos[2 * i], key = keys[e & 0xffu], used = (e >> 8) & 0xffu, off = e >> 16;
+        const uint32_t code = ls_class_code(key), s = ls_class_stage(key);
+        // (n: ls_classify positions this one covers, words: schedule words)
+        uint32_t okey = key, oe = e, n = 1, second = pos[2 * i + 1], words = used;
+        if (mode >= 1u && (code == OP_F || code == OP_G) && !ls_class_fused(key) && ls_fg_empty(s, mt, vlow)) {
+            if (drop)
+                drop[nd] = k;
+            ++nd;
+            k += used;
+            continue;
+        }
+        if (mode >= 1u && code == OP_COMB) {
+            uint32_t lo = off;
+            while (i + n < npos && s + n <= LS_RUN_MAXS) {
+                const uint32_t e2 = pos[2 * (i + n)], key2 = keys[e2 & 0xffu];
+                if (ls_class_code(key2) != OP_COMB || ls_class_stage(key2) != s + n ||
+                    (e2 >> 16) + (1u << (s + n - 1u)) != lo)
+                    break;
+                lo = e2 >> 16;
+                ++n;
+            }
+            // mode 2: the run (of one Combine too) and the G of the node's parent
+            bool rg = false;
+            if (mode >= 2u && i + n < npos && s + n <= LS_RUNG_MAXS) {
+                const uint32_t e3 = pos[2 * (i + n)], key3 = keys[e3 & 0xffu], sg = ls_class_stage(key3);
+                rg = ls_class_code(key3) == OP_G && sg == s + n && (e3 >> 16) == lo && sg < mt &&
+                     (ls_class_fused(key3) || !ls_fg_empty(sg, mt, vlow));
+                if (rg) {
+                    okey = LS_WK_RUNG | s << 8 | (key3 & 1u << 16) | n << 24;
+                    oe = (n + ((e3 >> 8) & 0xffu)) << 8 | lo << 16;
+                    second = pos[2 * (i + n) + 1];
+                    words = n + ((e3 >> 8) & 0xffu);
+                    n += 1; // (positions consumed)
+                }
+            }
+            if (!rg && n >= 2u) {
+                okey = LS_WK_RUN | s << 8 | n << 24;
+                oe = n << 8 | lo << 16;
+                second = 0u;
+                words = n;
+            } else if (!rg) {
+                n = 1;
+            }
+        }
+        uint32_t id = 0;
+        while (id < nc && ckeys[id] != okey)
+            ++id;
+        if (id == nc) {
+            if (nc == LS_MAXCLS)
+                return ~0u;
+            ckeys[nc++] = okey;
+        }
+        cpos[2 * np] = (oe & ~0xffu) | id;
+        cpos[2 * np + 1] = second;
+        if (first)
+            first[np] = k;
+        ++np;
+        k += words;
+        i += n - 1u;
+    }
+    *cncls = nc;
+    if (ndrop)
+        *ndrop = nd;
+    return np;
+}
+
 #ifdef PCG_RTC
 // Plan-specialised walk (rtc.cpp): the plan's schedule as literals (PCG_RTC_OPS).
 //   * PCG_RTC_CLASSES (default for LP <= 8): one inlined copy of ls_op per op class, its code,
@@ -3261,11 +3503,26 @@ struct RtcTab {
     uint32_t keys[LS_MAXCLS];
     uint32_t pos[2 * rtc_nops];
 };
+// PCG_RTC_COMPACT (rtc.cpp): 0 one position per ls_classify position, 1 the compacted table
+// (ls_compact: empty positions left out, Combine runs as one position), 2 a run and the G of its
+// node's parent one position too
+#ifndef PCG_RTC_COMPACT
+#define PCG_RTC_COMPACT 0
+#endif
 constexpr RtcTab rtc_make_tab()
 {
     RtcTab t{};
     t.npos = ls_classify(rtc_ops, rtc_nops, PCG_RTC_SL, rtc_mt, PCG_RTC_FUSE, t.keys, &t.ncls, t.pos);
+#if PCG_RTC_COMPACT
+    if (t.npos == ~0u)
+        return t;
+    RtcTab u{};
+    u.npos = ls_compact(t.keys, t.ncls, t.pos, t.npos, rtc_mt, PCG_RTC_V3, PCG_RTC_COMPACT, u.keys, &u.ncls, u.pos,
+                        nullptr, nullptr, nullptr);
+    return u;
+#else
     return t;
+#endif
 }
 constexpr RtcTab rtc_tab = rtc_make_tab();
 static_assert(rtc_tab.npos != ~0u && rtc_tab.ncls >= 1u, "more op classes than LS_MAXCLS (or none)");
@@ -3342,7 +3599,19 @@ PCG_DEV void ls_class_op(Ls<LP>& c, uint32_t cls, uint32_t o, uint32_t& P, uint3
 {
     if constexpr (HI - LO == 1u) {
         constexpr uint32_t key = rtc_tab.keys[LO];
-        ls_op_lit<LP, ls_class_code(key), ls_class_stage(key), ls_class_fused(key)>(c, o, P, desc);
+        if constexpr (ls_class_code(key) == LS_WK_RUN) { // (o: the run's last node)
+            ls_comb_run<LP, ls_class_stage(key), ls_class_len(key)>(c, o, c.p < P);
+            wsync();
+        } else if constexpr (ls_class_code(key) == LS_WK_RUNG) { // (o: the run's last node, the G's node)
+            constexpr uint32_t S0 = ls_class_stage(key), LEN = ls_class_len(key), SG = S0 + LEN;
+            if constexpr (ls_class_fused(key))
+                ls_fgf_op<OP_G, SG, S0, LEN>(c, SG, o, P);
+            else
+                ls_fg_op<OP_G, SG, S0, LEN>(c, SG, o, P);
+            wsync();
+        } else {
+            ls_op_lit<LP, ls_class_code(key), ls_class_stage(key), ls_class_fused(key)>(c, o, P, desc);
+        }
     } else {
         constexpr uint32_t MID = LO + (HI - LO) / 2u;
         if (cls < MID)
@@ -3805,6 +4074,24 @@ int sclls_rtc_classes(const uint32_t* ops, uint32_t nops, uint32_t log2N, uint32
         return -1;
     keys->assign(k, k + nc);
     return (int)np;
+}
+
+int sclls_rtc_walk(const uint32_t* ops, uint32_t nops, uint32_t log2N, uint32_t Sl, uint32_t virt, uint32_t v3,
+                   uint32_t fuse, uint32_t mode, std::vector<uint32_t>* keys, uint32_t* pos, uint32_t* first,
+                   std::vector<uint32_t>* dropped)
+{
+    const uint32_t mt = ls_mtop(log2N, virt);
+    std::vector<uint32_t> q(2 * (size_t)nops + 2), d(nops + 1);
+    uint32_t k[LS_MAXCLS], nc = 0, ck[LS_MAXCLS], cnc = 0, nd = 0;
+    const uint32_t np = ls_classify(ops, nops, Sl, mt, fuse, k, &nc, q.data());
+    if (np == ~0u)
+        return -1;
+    const uint32_t cnp = ls_compact(k, nc, q.data(), np, mt, v3, mode, ck, &cnc, pos, first, d.data(), &nd);
+    if (cnp == ~0u)
+        return -1;
+    keys->assign(ck, ck + cnc);
+    dropped->assign(d.begin(), d.begin() + nd);
+    return (int)cnp;
 }
 
 static uint32_t lp_of(uint32_t L)

@@ -187,6 +187,31 @@ def left_once_codes():
     ]
 
 
+def compact_codes():
+    """(N, L, frozen spec, crc, systematic): the list codes of tests/test_gpu_rtc_compact.py -- the
+    compacted walk table of the per-class walk (sclls_kernel.hip, PCG_RTC_COMPACT).  N = 32 to
+    1024, the quarters of N = 1024 stored (a leaf at stage top - 2) and recomputed, list sizes 2, 4, 5
+    and 8, one non-systematic.  Between them their walks hold every kind of position
+    (tests/test_rtc_compact.py): runs of Combines within one bit word, across words and over the
+    root's 32 words, ending the walk, in front of an empty G and of a recomputed quarter's G; runs
+    in front of a G reading LDS, reading the slab, and fused with its child's F, reached with few
+    paths (the Bhattacharyya sets: their first information bits come late) and with a full list
+    (the random sets).  All of them are class_codes', stream_codes' or config 3."""
+    hs = tuple(high_leaf_set(1024))
+    rnd = {(N, L): tuple(fr) for N, L, fr in random_list_codes()}
+    return [
+        (32, 2, ("BB", 16), 8, True),
+        (64, 5, ("BB", 32), 8, True),
+        (256, 8, ("BB", 128), 8, False),
+        (512, 4, ("set", stream_codes()[1][2][1]), 0, True),
+        (512, 8, ("BB", 256), 8, True),
+        (1024, 8, ("set", hs), 8, True),
+        (1024, 4, ("set", rnd[(1024, 4)]), 0, True),
+        (1024, 2, ("BB", 512), 8, True),
+        (1024, 8, ("BB", 512), 8, True),                  # config 3
+    ]
+
+
 def validation_codes():
     """The codes the GPU parity tests run through specialised kernels (tests/test_gpu_rtc.py,
     tests/test_gpu_char.py and the specialised variants of the full-size parity tests)."""
@@ -206,6 +231,7 @@ def validation_codes():
     out += class_codes()                                  # the specialised walk's op classes
     out += stream_codes()                                 # its literal streaming forms
     out += left_once_codes()                              # the left child staged once per codeword
+    out += compact_codes()                                # the compacted walk table
     out.append((1024, 8, ("5G", 512), 0, True))           # config 4's decoder core with the Dummy detector
     out.append((1024, 1, ("5G", 512), 11, True))          # config 4 through Fast-SSC
     for crc in (8, 16, 32):                               # AdaptiveFloat: both stages
