@@ -126,6 +126,7 @@ def lib():
         L.pcg_ask_constants.argtypes = [C.c_uint32, P, P]
         L.pcg_ask_channel_f32.argtypes = [P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float,
                                           C.c_uint64, P, P, P]
+        L.pcg_dev_polar_f.argtypes = [P, P, P, C.c_size_t, P, C.POINTER(C.c_int)]
         _lib = L
     return _lib
 
@@ -168,6 +169,20 @@ def _stream(stream, t):
         return stream
     import torch
     return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def dev_polar_f(a, b, stream=None):
+    """Development aid (pcg_dev_polar_f): the kernels' min-sum F, wave.hpp polar_f, applied
+    elementwise to two float32 cuda tensors of one shape, on `stream` (default: torch's current
+    one).  Returns (out, form): the result tensor and the library's PCG_F_FORM."""
+    import torch
+    dev = a.device.index if a.device.index is not None else torch.cuda.current_device()
+    _check_tensor("a", a, torch.float32, a.shape, dev)
+    _check_tensor("b", b, torch.float32, a.shape, dev)
+    out = torch.empty_like(a)
+    form = C.c_int(0)
+    _check(lib().pcg_dev_polar_f(_ptr(a), _ptr(b), _ptr(out), a.numel(), _stream(stream, a), C.byref(form)))
+    return out, form.value
 
 
 def _frozen_array(frozen):

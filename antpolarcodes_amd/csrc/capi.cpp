@@ -721,6 +721,22 @@ int pcg_dev_rtc_walk(const pcg_plan* p, int mode, uint32_t* keys, int nkeys, int
     return n;
 }
 
+// Development aid, not part of include/pcg.h: out[i] = polar_f(a[i], b[i]) (wave.hpp) for n
+// device floats on `stream`, asynchronously -- the min-sum F by itself, below every decoder.
+// *form (may be null) = the PCG_F_FORM the library's list kernel was built with.
+int pcg_dev_polar_f(const float* a, const float* b, float* out, size_t n, void* stream, int* form)
+{
+    if (n && (!a || !b || !out))
+        return fail(PCG_E_ARG, "null argument");
+    int f = 0;
+    const int rc = pcg::launch_polar_f_dev(a, b, out, n, &f, reinterpret_cast<hipStream_t>(stream));
+    if (form)
+        *form = f;
+    if (rc != 0)
+        return fail(rc, rc == -4 ? "polar_f: n > 2^31" : std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return PCG_OK;
+}
+
 // Development aid, not part of include/pcg.h: hiprtc compiles this process started.
 int pcg_dev_rtc_compiles(void) { return pcg::rtc_compiles(); }
 

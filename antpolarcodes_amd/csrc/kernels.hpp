@@ -120,6 +120,9 @@ int sclls_layout(uint32_t N, uint32_t L, uint32_t lp, uint32_t vleaf, uint32_t* 
                  uint32_t* lds_stage_limit, uint64_t* scratch_floats, uint32_t* virt, uint32_t* v3, uint32_t* sb);
 uint64_t sclls_wave_cap(uint32_t lp, uint32_t wave_lds_floats);
 int launch_sclls(const KernelArgs& a, hipStream_t stream);
+// development aid: out[i] = polar_f(a[i], b[i]), n device floats, in the PCG_F_FORM of the list
+// kernel's translation unit; *form = that form
+int launch_polar_f_dev(const float* a, const float* b, float* out, uint64_t n, int* form, hipStream_t stream);
 // 8-bit SCL (scl_char_kernel.hip): LDS dwords per wave, LDS stage limit, global scratch dwords
 int sclc_layout(uint32_t N, uint32_t L, uint32_t* lds_dwords, uint32_t* Sl, uint64_t* scratch_dwords);
 uint64_t sclc_wave_cap(uint32_t L, uint32_t lds_dwords, bool i8);

@@ -4034,7 +4034,7 @@ std::string sclls_rtc_defines(bool* nondefault)
     d("PCG_STG_GM", PCG_STG_GM, 1);
     d("PCG_STG_DB", PCG_STG_DB, 1);
     d("PCG_DEEP_SHARE", PCG_DEEP_SHARE, 1);
-    d("PCG_F_OLD", PCG_F_OLD, 0);
+    d("PCG_F_FORM", PCG_F_FORM, 2);
     d("PCG_SEL_TOP8", PCG_SEL_TOP8, 1);
     d("PCG_STG_SHARED_F", PCG_STG_SHARED_F, 1);
     d("PCG_STG_LEFT_ONCE", PCG_STG_LEFT_ONCE, 1);
@@ -4153,6 +4153,28 @@ int launch_sclls(const KernelArgs& a, hipStream_t stream)
     case 32: return sclls_launch_32(a, lds, stream);
     default: return -4;
     }
+}
+
+// development aid (capi.cpp pcg_dev_polar_f): wave.hpp's polar_f by itself, below every decoder,
+// so that its +-0 / denormal / infinity behaviour is pinned on the device.  It lives here so
+// that a dev build of this file (tools/build_dev_lib.sh ... -DPCG_F_FORM=...) carries the form
+// in the list kernel and in this entry alike.
+__global__ void __launch_bounds__(256) polar_f_dev_kernel(const float* a, const float* b, float* out, uint64_t n)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i < n)
+        out[i] = polar_f(a[i], b[i]);
+}
+
+int launch_polar_f_dev(const float* a, const float* b, float* out, uint64_t n, int* form, hipStream_t stream)
+{
+    *form = PCG_F_FORM;
+    if (n == 0)
+        return 0;
+    if (n > (1ull << 31)) // (the grid's x dimension)
+        return -4;
+    hipLaunchKernelGGL(polar_f_dev_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, a, b, out, n);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 #endif // PCG_LS_HOST

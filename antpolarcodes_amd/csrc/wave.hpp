@@ -39,25 +39,48 @@ PCG_DEV float minps(float a, float b) { return a < b ? a : b; }
 PCG_DEV float maxps(float a, float b) { return a > b ? a : b; }
 
 // f: sign(a)^sign(b) | min(|a|,|b|)          avx_float.h:55-63
-// MINPS semantics (the second operand on ties and NaN): the compare takes abs source modifiers
-// and the select picks the SIGNED operand whose magnitude wins, so the sign merge is one bit
-// select -- v_cmp_lt |a|,|b|; v_cndmask; v_xor; v_bfi (4 VALU; selecting |a| / |b| instead
-// made the compiler add a v_and per element: 5)
-#ifndef PCG_F_OLD
-#define PCG_F_OLD 0 // dev A/B: 1 = the round-4 formulation (abs values selected: 5 VALU)
+// The VALU instructions per element are PCG_F_FORM (a compile-time switch, so one tree gives all
+// forms for an A/B: -DPCG_F_FORM=... in a dev library build and, for the hiprtc kernels,
+// sclls_rtc_defines / PCG_RTC_XOPTS):
+//   2  F = clamp(b, -|a|, +|a|) with the sign of a XORed in:
+//        v_med3_f32 |a|, b, -|a| (abs / neg source modifiers); v_bitop3 0x78 (S0 ^ (S1 & S2)).
+//        For a != 0 the median is b, +|a| or -|a| bit for bit.  For a = +-0 it must be the zero
+//        with b's sign, which holds only if the median orders -0 below +0 AND the operands
+//        stand in this order: the ISA manual's v_med3_f32 picks by which operand equals
+//        the maximum and then takes a v_max (-0 < +0 stated); (|a|, b, -|a|) gives the wanted
+//        zero in all four sign cases, (b, -|a|, |a|) gives +0 for b < 0.  Infinities and
+//        denormals pass unchanged (tests/test_gpu_polar_f.py pins all of this on the device).
+//        NaN differs from MINPS when b is NaN: the median falls back to the minimum of the
+//        non-NaN operands (-|a|), MINPS returns b.  NaN LLRs are in no contract item.
+//   3  v_min_f32 |a|, |b|; v_xor; v_bitop3 0xE4.  (Inline asm: __builtin_fminf gets a
+//        canonicalising v_max_f32 x, x in front.)  Both operands of the minimum are
+//        non-negative, so there is no ordering question; b NaN gives |a| where MINPS gives b.
+//   4  MINPS semantics (the second operand on ties and NaN): the compare takes abs source
+//        modifiers and the select picks the SIGNED operand whose magnitude wins, so the sign
+//        merge is one bit select -- v_cmp_lt |a|,|b|; v_cndmask; v_xor; v_bitop3 0xE4.
+#ifndef PCG_F_FORM
+#define PCG_F_FORM 2
+#endif
+#if PCG_F_FORM != 2 && PCG_F_FORM != 3 && PCG_F_FORM != 4
+#error "PCG_F_FORM is 2 (median), 3 (v_min) or 4 (compare + select)"
 #endif
 PCG_DEV float polar_f(float a, float b)
 {
-#if PCG_F_OLD
-    const float aa = __builtin_fabsf(a), ab = __builtin_fabsf(b);
-    return ubits(((fbits(a) ^ fbits(b)) & 0x80000000u) | fbits(aa < ab ? aa : ab));
-#endif
+    // truth tables: bit i = f(S0 = i>>2 & 1, S1 = i>>1 & 1, S2 = i & 1); 0xE4 = S2 ? S0 : S1
+    // (written as the builtin: the compiler turns the plain expression back into and + and_or)
+#if PCG_F_FORM == 2
+    const float m = __builtin_amdgcn_fmed3f(__builtin_fabsf(a), b, -__builtin_fabsf(a));
+    return ubits(__builtin_amdgcn_bitop3_b32(fbits(m), fbits(a), 0x80000000u, 0x78));
+#elif PCG_F_FORM == 3
+    float m;
+    asm("v_min_f32 %0, |%1|, |%2|" : "=v"(m) : "v"(a), "v"(b));
+    return ubits(__builtin_amdgcn_bitop3_b32(fbits(a) ^ fbits(b), fbits(m), 0x80000000u, 0xE4));
+#else
     const uint32_t ua = fbits(a), ub = fbits(b);
     const uint32_t sel = __builtin_fabsf(a) < __builtin_fabsf(b) ? ua : ub;
-    // S2 ? S0 : S1 with S2 = the sign mask: the sign of a ^ b, the rest of sel (truth table
-    // 0xE4: bit i = f(S0 = i>>2 & 1, S1 = i>>1 & 1, S2 = i & 1), the convention of 0x78 below)
-    // (written as the builtin: the compiler turns the plain expression back into and + and_or)
+    // the sign of a ^ b, the rest of sel
     return ubits(__builtin_amdgcn_bitop3_b32(ua ^ ub, sel, 0x80000000u, 0xE4));
+#endif
 }
 // g: (a ^ signbit) + b                       avx_float.h:71-81
 PCG_DEV float polar_g(float a, float b, uint32_t signbit) { return fxor(a, signbit) + b; }

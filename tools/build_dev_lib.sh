@@ -7,6 +7,9 @@
 # the objects sclls_kernel.hip.o and sclls_lp<LP>.o; its specialised (hiprtc) kernels carry the
 # same -D knobs (sclls_rtc_defines).  Plans of the other list widths are refused by such a library
 # (PCG_E_UNSUPPORTED at creation: their objects were built with the default knobs).
+# The min-sum F forms (wave.hpp PCG_F_FORM): `build_dev_lib.sh f4 sclls_kernel.hip -DPCG_F_FORM=4` gives
+# the list kernel, its specialised kernels and pcg_dev_polar_f in form 4; the Fast-SSC specialised
+# kernel carries no knobs in its source and takes PCG_RTC_XOPTS=-DPCG_F_FORM=4 beside it.
 set -e
 TAG=$1; SRC=$2; shift 2
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
